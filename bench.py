@@ -11,6 +11,14 @@ Strong scaling: the 512^3 problem is partitioned in row blocks across ranks.
 Single GPU:  python bench.py [--size 512 --steps 1 --warmup 1]
 Multi GPU :  python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
                  --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the steps and prints one JSON line.
+--dump-outputs DIR additionally writes what the last timed step returned
+(x.npy, iters.npy, resid.npy) so two builds can be compared output for
+output; the inputs are seeded and identical from run to run.
+--full is reserved for secondary measurements (other configurations,
+baselines, per-kernel figures); none live in this file today — they are
+separate tools under scripts/ — so it currently adds nothing to a plain run.
 """
 import argparse
 import json
@@ -42,11 +50,40 @@ def parse_args():
     p.add_argument("--weak", action="store_true",
                    help="weak scaling: size^3 unknowns PER RANK (domain grows "
                         "along z); default is strong scaling at size^3 total")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's outputs "
+                        "(x, iters, resid) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the benchmark's secondary measurements "
+                        "(none at present; a plain run is the headline only)")
     return p.parse_args()
 
 
-def one_step(args, dist_ctx):
-    """Full setup+solve; returns (elapsed_s, setup_s, solve_s, iters, resid, true_rel)."""
+# --dump-outputs keeps x whole up to this many entries (32 MiB of fp64);
+# a longer x is reduced to a fixed, seeded sample of this many entries
+DUMP_MAX_ENTRIES = 1 << 22
+
+
+def dump_outputs(path, x, iters, resid):
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    if hasattr(x, "cpu"):
+        x = x.cpu().numpy()
+    x = np.asarray(x, dtype=np.float64).ravel()
+    if x.size > DUMP_MAX_ENTRIES:
+        idx = np.random.default_rng(0).integers(0, x.size, size=DUMP_MAX_ENTRIES)
+        idx.sort()
+        x = x[idx]
+    np.save(os.path.join(path, "x.npy"), x)
+    np.save(os.path.join(path, "iters.npy"), np.array([iters], dtype=np.float64))
+    np.save(os.path.join(path, "resid.npy"), np.array([resid], dtype=np.float64))
+
+
+def one_step(args, dist_ctx, want_x=False):
+    """Full setup+solve; returns (elapsed_s, setup_s, solve_s, iters, resid,
+    true_rel, x) where x is the full solution as the solver returned it (host
+    array or device tensor) if want_x, else None."""
     import numpy as np
 
     import amgcl_amd as am
@@ -95,8 +132,10 @@ def one_step(args, dist_ctx):
             xh = solve.backend.to_host(x)
             true_rel = float(np.linalg.norm(b - A @ xh) / np.linalg.norm(b))
     else:
-        t0, t1, t2, iters, resid, true_rel = run_distributed(args, dist_ctx)
-    return t2 - t0, t1 - t0, t2 - t1, iters, resid, true_rel
+        t0, t1, t2, iters, resid, true_rel, x = run_distributed(args, dist_ctx)
+    if not want_x:
+        x = None
+    return t2 - t0, t1 - t0, t2 - t1, iters, resid, true_rel, x
 
 
 def run_distributed(args, dist_ctx):
@@ -214,7 +253,7 @@ def run_distributed(args, dist_ctx):
         nums = nums.cuda()  # NCCL collectives need device tensors
     dist.all_reduce(nums)
     true_rel = float((nums[0] / nums[1]).sqrt())
-    return t0, t1, t2, iters, resid, true_rel
+    return t0, t1, t2, iters, resid, true_rel, x_full
 
 
 def _has_gpu():
@@ -256,8 +295,11 @@ def main():
         dist.barrier()
     times, setups, solves, iters_l, resid, true_rel = [], [], [], [], 0.0, 0.0
     t_start = time.perf_counter()
-    for _ in range(args.steps):
-        el, setup_s, solve_s, iters, resid, true_rel = one_step(args, dist_ctx)
+    x = None
+    for i in range(args.steps):
+        el, setup_s, solve_s, iters, resid, true_rel, x = one_step(
+            args, dist_ctx,
+            want_x=bool(args.dump_outputs) and i == args.steps - 1)
         times.append(el)
         setups.append(setup_s)
         solves.append(solve_s)
@@ -272,6 +314,9 @@ def main():
                          device="cuda" if _has_gpu() else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         total = float(t.item())
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, x, iters_l[-1], resid)
 
     if rank == 0:
         value = total / args.steps

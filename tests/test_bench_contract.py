@@ -92,3 +92,58 @@ def test_bench_single_process_contract():
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert d["n_gpus"] == 1
     assert d["config"]["true_rel_resid"] < 1e-6
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes what the last timed step returned; the inputs
+    are seeded, so the dumped x must solve the same system rebuilt here.
+    --full is accepted alongside and keeps the single result line."""
+    import subprocess
+
+    import amgcl_amd as am
+
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+    out_dir = tmp_path / "dump"
+    r = subprocess.run(
+        [sys.executable, "bench.py", "--size", "16", "--steps", "2",
+         "--warmup", "0", "--backend", "cpu", "--full",
+         "--dump-outputs", str(out_dir)],
+        capture_output=True, text=True, timeout=300,
+        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 0
+    assert abs(d["ms_per_step"] - d["value"] * 1000) < 1e-9
+    assert sorted(p.name for p in out_dir.iterdir()) == [
+        "iters.npy", "resid.npy", "x.npy"]
+    x = np.load(out_dir / "x.npy")
+    iters = np.load(out_dir / "iters.npy")
+    resid = np.load(out_dir / "resid.npy")
+    assert x.dtype == np.float64 and x.shape == (16 ** 3,)
+    assert iters.dtype == np.float64 and resid.dtype == np.float64
+    assert int(iters[0]) == d["config"]["iters"]
+    assert float(resid[0]) == d["config"]["final_rel_resid"]
+    A, b = am.poisson3d(16, rhs="random")
+    assert np.linalg.norm(b - A @ x) / np.linalg.norm(b) < 1e-6
+
+
+def test_bench_dump_sample_is_fixed(tmp_path):
+    """An output longer than the cap is reduced to a fixed, seeded sample:
+    same entries on every call, in increasing index order."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+
+    n = bench.DUMP_MAX_ENTRIES + 12345
+    x = np.arange(n, dtype=np.float64)
+    bench.dump_outputs(str(tmp_path / "a"), x, 7, 1e-7)
+    bench.dump_outputs(str(tmp_path / "b"), x, 7, 1e-7)
+    a = np.load(tmp_path / "a" / "x.npy")
+    b = np.load(tmp_path / "b" / "x.npy")
+    assert a.shape == (bench.DUMP_MAX_ENTRIES,) and a.dtype == np.float64
+    assert np.array_equal(a, b)
+    assert np.all(np.diff(a) >= 0) and a[0] >= 0 and a[-1] < n
+    assert a.nbytes <= 64 * 2 ** 20
