@@ -65,6 +65,13 @@ _SIGS = {
     "amg_sptrsv_f64": [ctypes.c_int64] + [ctypes.c_void_p] * 7
                       + [ctypes.c_int, ctypes.c_void_p],
     "amg_coop_supported": [],
+    # block (BSR) twin: nlev, lptr, rows, bsize, ptr, col, val, dinv, z,
+    # lower, max_blocks, stream
+    "amg_bsr_sptrsv_f64": [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                           ctypes.c_int] + [ctypes.c_void_p] * 5
+                          + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p],
+    "amg_bsr_sptrsv_geometry": [ctypes.c_int, ctypes.c_int]
+                               + [ctypes.c_void_p] * 3,
     # --- complex128 solve kernels (host complex setup + device solve) ---
     "amg_spmv_c128": [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 4
                      + [ctypes.c_double] * 4 + [ctypes.c_void_p, ctypes.c_int,

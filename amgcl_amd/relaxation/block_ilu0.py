@@ -5,10 +5,12 @@ Parity: amgcl/relaxation/ilu0.hpp:51 instantiated over
 reference's block-valued ILU route used by the CoupCons3D tutorial.  The
 factorization runs over b×b blocks on the host (`_core.block_ilu0_factor`,
 inverted diagonal blocks via Gauss-Jordan = detail/inverse.hpp:45); the
-apply is serial block sweeps on the CPU backend and, on the GPU, the
-reference's damped-Jacobi iterated approximate triangular solves
+apply is serial block sweeps on the CPU backend and, on the GPU, either
+the reference's damped-Jacobi iterated approximate triangular solves
 (detail/ilu_solve.hpp:44-124) composed from the BSR SpMV and
-block-diagonal-multiply kernels (csrc/hip/block.hip).
+block-diagonal-multiply kernels (csrc/hip/block.hip), or with
+``solve="exact"`` the exact level-scheduled block solve: one cooperative
+kernel per factor (csrc/hip/block_sptrsv.hip), any block size 1..8.
 """
 import numpy as np
 
@@ -22,8 +24,12 @@ class BlockILU0:
 
     @staticmethod
     def defaults():
+        # solve="jacobi": iterated approximate triangular solves on the GPU;
+        # solve="exact": exact level-scheduled block solve by one cooperative
+        # GPU kernel per factor. The CPU backend's serial sweeps are exact
+        # under either value.
         return {"block_size": 2, "damping": 1.0,
-                "solve_iters": 2, "solve_damping": 0.72}
+                "solve_iters": 2, "solve_damping": 0.72, "solve": "jacobi"}
 
     def __init__(self, A, prm, backend):
         if not isinstance(A, CSR):
@@ -38,6 +44,10 @@ class BlockILU0:
             raise ValueError("block_ilu0 needs 1 <= block_size <= 8")
         if A.nrows % b:
             raise ValueError("matrix size not divisible by block_size")
+        if str(p["solve"]) not in ("jacobi", "exact"):
+            raise ValueError(f"block_ilu0 solve must be jacobi|exact, "
+                             f"got '{p['solve']}'")
+        self._exact = str(p["solve"]) == "exact"
         self.damping = float(p["damping"])
         self.backend = backend
         self.n = A.nrows
@@ -85,10 +95,70 @@ class BlockILU0:
             # diagonal blocks, already inverted by the factorization
             self.Dinv = torch.from_numpy(
                 np.ascontiguousarray(blocks[dia].ravel())).to(dev)
-            self._t0 = backend.vector(self.n)
-            self._t1 = backend.vector(self.n)
-            self._t2 = backend.vector(self.n)
-            self._t3 = backend.vector(self.n)
+            if self._exact:
+                self._setup_exact(bp, bc, dia)
+            else:
+                self._t0 = backend.vector(self.n)
+                self._t1 = backend.vector(self.n)
+                self._t2 = backend.vector(self.n)
+                self._t3 = backend.vector(self.n)
+
+    def _setup_exact(self, bp, bc, dia):
+        """Level schedules over block rows for the two factors, uploaded."""
+        import ctypes
+
+        import torch
+
+        from ..backend._hiplib import check, lib
+
+        if not lib().amg_coop_supported():
+            raise RuntimeError("exact GPU block sptrsv needs cooperative launch")
+        dia32 = np.ascontiguousarray(dia, dtype=np.int32)
+        lp, lr = _core.tri_levels(self.nb, bp, bc, dia32, True)
+        up, ur = _core.tri_levels(self.nb, bp, bc, dia32, False)
+        lp, up = np.asarray(lp), np.asarray(up)
+        dev = self.backend.device
+        self._lev = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                          for a in (lp, lr, up, ur))
+        self._nlev = (len(lp) - 1, len(up) - 1)
+        # The grid barrier costs more the more workgroups take part (measured
+        # on the MI355X: about 7 us plus 0.1 us per workgroup and level, see
+        # profiles/README.md), so a grid sized by occupancy spends its time
+        # in the barrier. Ask for enough workgroups to cover twice the mean
+        # level in one pass, and never more than the widest level can occupy.
+        grid, block, group = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        check(lib().amg_bsr_sptrsv_geometry(
+            self.b, 1, ctypes.byref(grid), ctypes.byref(block),
+            ctypes.byref(group)), "bsr_sptrsv_geometry")
+        per_block = block.value // group.value
+
+        def blocks(levptr):
+            if len(levptr) < 2:
+                return 1
+            width = np.diff(levptr)
+            want = -(-2 * int(np.ceil(width.mean())) // per_block)
+            return max(1, min(want, -(-int(width.max()) // per_block)))
+
+        self._max_blocks = (blocks(lp), blocks(up))
+
+    def _solve_exact(self, z):
+        """Exact level-scheduled block triangular solves on the GPU, in place
+        (one cooperative kernel per factor, the arithmetic of the serial
+        sweeps — see block_sptrsv.hip bsr_sptrsv_levels_k)."""
+        from ..backend._hiplib import check, lib
+        from ..backend.hip import _stream
+
+        lp, lr, up, ur = self._lev
+        check(lib().amg_bsr_sptrsv_f64(
+            self._nlev[0], lp.data_ptr(), lr.data_ptr(), self.b,
+            self.L.ptr.data_ptr(), self.L.col.data_ptr(), self.L.val.data_ptr(),
+            0, z.data_ptr(), 1, self._max_blocks[0], _stream()),
+            "bsr_sptrsv_lower")
+        check(lib().amg_bsr_sptrsv_f64(
+            self._nlev[1], up.data_ptr(), ur.data_ptr(), self.b,
+            self.U.ptr.data_ptr(), self.U.col.data_ptr(), self.U.val.data_ptr(),
+            self.Dinv.data_ptr(), z.data_ptr(), 0, self._max_blocks[1],
+            _stream()), "bsr_sptrsv_upper")
 
     def _blkdiag(self, x, y):
         from ..backend._hiplib import check, lib
@@ -127,6 +197,8 @@ class BlockILU0:
         if self._serial:
             _core.block_ilu0_solve(self.nb, self.b, self.bptr, self.bcol,
                                    self.lu, self.dia, tmp)
+        elif self._exact:
+            self._solve_exact(tmp)
         else:
             self._solve_jacobi(tmp)
         b.axpby(self.damping, tmp, 1.0, x)
