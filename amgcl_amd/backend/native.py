@@ -81,6 +81,16 @@ def _bind():
     global _driver_bound
     L = _lib()
     if not _driver_bound:
+        # LevelDescC above is a hand-kept copy of the C struct (amg_common.h):
+        # refuse to pass it on if the two disagree on the size or on where
+        # the last field sits
+        theirs = (L.amg_leveldesc_size(), L.amg_leveldesc_last_offset())
+        ours = (ctypes.sizeof(LevelDescC), LevelDescC.ilu_b.offset)
+        if theirs != ours:
+            raise RuntimeError(
+                f"LevelDesc layout mismatch: libamghip.so has size {theirs[0]}, "
+                f"ilu_b at {theirs[1]}; LevelDescC has size {ours[0]}, ilu_b at "
+                f"{ours[1]}")
         L.amg_driver_create.argtypes = [
             ctypes.POINTER(LevelDescC), ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,

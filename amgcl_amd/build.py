@@ -24,6 +24,11 @@ def _newer(target, sources):
     return all(os.path.getmtime(s) <= t for s in sources)
 
 
+def _headers(directory):
+    return sorted(os.path.join(directory, f) for f in os.listdir(directory)
+                  if f.endswith((".h", ".hpp")))
+
+
 def build_core_ext(verbose=True):
     import pybind11
 
@@ -56,7 +61,9 @@ def build_hip_lib(verbose=True):
     out_dir = os.path.join(PKG_DIR, "_hip")
     os.makedirs(out_dir, exist_ok=True)
     out = os.path.join(out_dir, "libamghip.so")
-    if _newer(out, srcs + [__file__]):
+    # capi_gpu.hip also includes the host setup engine from csrc/capi
+    deps = _headers(hip_dir) + [os.path.join(PKG_DIR, "csrc", "capi", "amgcl_host.hpp")]
+    if _newer(out, srcs + deps + [__file__]):
         return out
     cmd = [
         HIPCC, f"--offload-arch={GPU_ARCH}", "-O3", "-std=c++17",
@@ -78,7 +85,7 @@ def build_capi_lib(verbose=True):
     out_dir = os.path.join(PKG_DIR, "_capi")
     os.makedirs(out_dir, exist_ok=True)
     out = os.path.join(out_dir, "libamgclamd_c.so")
-    if _newer(out, [src, __file__]):
+    if _newer(out, [src, __file__] + _headers(os.path.dirname(src))):
         return out
     cmd = [
         "g++", "-O3", "-std=c++17", "-shared", "-fPIC", "-fopenmp",

@@ -20,6 +20,8 @@
 
 #include <cstdint>
 
+#include "amg_kernels.h"
+
 static inline int nblk_b(int64_t work, int block = 256, int cap = 4096) {
     int64_t b = (work + block - 1) / block;
     return (int)(b < 1 ? 1 : (b > cap ? cap : b));

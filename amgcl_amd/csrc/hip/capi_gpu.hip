@@ -20,63 +20,7 @@
 
 #include "../capi/amgcl_host.hpp"
 #include "amg_common.h"
-
-extern "C" void *amg_driver_create(const LevelDesc *levels, int nlevels,
-                                   const void *coarse_inv, int64_t ncoarse, int npre,
-                                   int npost, int ncycle, int pre_cycles, int f32,
-                                   int64_t a64_nnz, const int *a64_ptr,
-                                   const int *a64_col, const double *a64_val,
-                                   int a64_subw, hipStream_t stream);
-extern "C" void amg_driver_destroy(void *h);
-// device setup engine (setup.hip)
-extern "C" int amg_setup_diag(int64_t n, const int *ptr, const int *col,
-                              const double *val, double *d, hipStream_t s);
-extern "C" int amg_setup_strong(int64_t n, const int *ptr, const int *col,
-                                const double *val, const double *d, double eps2,
-                                uint8_t *S, hipStream_t s);
-extern "C" int amg_setup_spai0(int64_t n, const int *ptr, const int *col,
-                               const double *val, double *m, hipStream_t s);
-extern "C" int amg_agg_init(int64_t n, const int *ptr, const uint8_t *S, int *id,
-                            hipStream_t s);
-extern "C" int amg_agg_run(int64_t n, const int *ptr, const int *col, const uint8_t *S,
-                           int *id, uint8_t *prov, uint64_t *m1, uint8_t *newroot,
-                           uint8_t *near, int *remaining, int sync_stride,
-                           int max_rounds, int *rounds_out, int *lists, hipStream_t s);
-extern "C" int amg_agg_renumber(int64_t n, int *id, int *mark, hipStream_t s);
-extern "C" int amg_psmooth_count(int64_t n, const int *ptr, const int *col,
-                                 const uint8_t *S, const int *id, int *cnt,
-                                 int *overflow, hipStream_t s);
-extern "C" int amg_psmooth_fill(int64_t n, const int *ptr, const int *col,
-                                const double *val, const uint8_t *S, const int *id,
-                                double omega, const int *pptr_scanned, int *pcol,
-                                double *pval, hipStream_t s);
-extern "C" int amg_transpose_count(int64_t nnz, const int *col, int *tcnt,
-                                   hipStream_t s);
-extern "C" int amg_transpose_scatter(int64_t n, const int *ptr, const int *col,
-                                     const double *val, int *cursor, int *tcol,
-                                     double *tval, hipStream_t s);
-extern "C" int amg_spgemm_count(int64_t an, const int *aptr, const int *acol,
-                                const int *bptr, const int *bcol, int *ub, int *cnt,
-                                int *overflow, int *bigscratch, hipStream_t s);
-extern "C" int amg_spgemm_fill(int64_t an, const int *aptr, const int *acol,
-                               const double *aval, const int *bptr, const int *bcol,
-                               const double *bval, const int *ub,
-                               const int *cptr_scanned, int *ccol, double *cval,
-                               int do_sort, const int *bigscratch, hipStream_t s);
-extern "C" int amg_scan_i32(int *a, int64_t n, hipStream_t s);
-extern "C" int amg_sell_fill_f64(int64_t nrows, int64_t nslice, const int *ptr,
-                                 const int *col, const double *val,
-                                 const int64_t *soff, const int *srows, int *scol,
-                                 double *sval, hipStream_t stream);
-extern "C" int amg_driver_cg(void *h, const double *rhs, double *x, double *r,
-                             double *s, double *p, double *q, double *s_swap,
-                             double tol, double abstol, int maxiter,
-                             int64_t *iters_out, double *resid_out);
-extern "C" int amg_driver_bicgstab(void *h, const double *rhs, double *x, double *r,
-                                   double *p, double *v, double *s2, double *t2,
-                                   double *rh, double *T, double *T_swap, double tol,
-                                   double abstol, int maxiter, int64_t *iters_out,
-                                   double *resid_out);
+#include "amg_kernels.h"
 
 namespace {
 

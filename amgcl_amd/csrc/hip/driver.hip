@@ -10,188 +10,46 @@
 // Per-level relaxation uses a pointer-swapping fused kernel
 //   x_new = x + M ∘ (rhs - A x)
 // so the separate axpby pass of the generic path disappears.
+//
+// Launchers from the other .hip files come from amg_kernels.h.  Each entry
+// point is enter_driver -> body -> finish(), so every return of a body, an
+// error included, leaves through the same stream hand-back.
 
 #include <hip/hip_runtime.h>
 
 #include "amg_common.h"
+#include "amg_kernels.h"
 
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstdlib>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
-// kernels.hip exports
-extern "C" int amg_spmv_f64(int64_t, int64_t, const int *, const int *, const double *,
-                            const double *, double, double, double *, int, hipStream_t);
-extern "C" int amg_residual_f64(int64_t, int64_t, const int *, const int *, const double *,
-                                const double *, const double *, double *, int, hipStream_t);
-extern "C" int amg_axpby_f64(int64_t, double, const double *, double, double *, hipStream_t);
-extern "C" int amg_axpbypcz_f64(int64_t, double, const double *, double, const double *,
-                                double, double *, hipStream_t);
-extern "C" int amg_fill_f64(int64_t, double, double *, hipStream_t);
-extern "C" int amg_dot_f64(int64_t, const double *, const double *, double *, hipStream_t);
-extern "C" int amg_dot2_f64(int64_t, const double *, const double *, const double *,
-                            const double *, double *, hipStream_t);
-extern "C" int amg_gemv_f64(int64_t, const double *, const double *, double *, hipStream_t);
-extern "C" int amg_cg_tail_f64(int64_t, double, const double *, const double *, double *,
-                               double *, double *, hipStream_t);
-extern "C" int amg_vmul_f64(int64_t, double, const double *, const double *, double,
-                            double *, hipStream_t);
-extern "C" int amg_spmv_f32(int64_t, int64_t, const int *, const int *, const float *,
-                            const float *, double, double, float *, int, hipStream_t);
-extern "C" int amg_residual_f32(int64_t, int64_t, const int *, const int *, const float *,
-                                const float *, const float *, float *, int, hipStream_t);
-extern "C" int amg_gemv_f32(int64_t, const float *, const float *, float *, hipStream_t);
-extern "C" int amg_cast_d2s(int64_t, const double *, float *, hipStream_t);
-extern "C" int amg_cast_s2d(int64_t, const float *, double *, hipStream_t);
-extern "C" int amg_sell_spmv_f64(int64_t, int64_t, const int64_t *, const int *,
-                                 const double *, const int *, const double *, double,
-                                 double, double *, hipStream_t);
-extern "C" int amg_sell_spmv_f32(int64_t, int64_t, const int64_t *, const int *,
-                                 const float *, const int *, const float *, double,
-                                 double, float *, hipStream_t);
-extern "C" int amg_bsr_spmv_f64(int64_t, int, const int *, const int *,
-                                const double *, const double *, double, double,
-                                double *, hipStream_t);
-extern "C" int amg_bsr_residual_f64(int64_t, int, const int *, const int *,
-                                    const double *, const double *, const double *,
-                                    double *, hipStream_t);
-extern "C" int amg_bsr_relax_f64(int64_t, int, const int *, const int *,
-                                 const double *, const double *, const double *,
-                                 const double *, double *, hipStream_t);
-extern "C" int amg_axpby_f32(int64_t, double, const float *, double, float *,
-                             hipStream_t);
-extern "C" int amg_vmul_f32(int64_t, double, const float *, const float *, double,
-                            float *, hipStream_t);
-extern "C" int amg_fill_f32(int64_t, double, float *, hipStream_t);
-extern "C" int amg_sell_residual_f64(int64_t, int64_t, const int64_t *, const int *,
-                                     const double *, const int *, const double *,
-                                     const double *, double *, hipStream_t);
-extern "C" int amg_sell_relax_f64(int64_t, int64_t, const int64_t *, const int *,
-                                  const double *, const int *, const double *,
-                                  const double *, const double *, double *,
-                                  hipStream_t);
-extern "C" int amg_sell_residual_f32(int64_t, int64_t, const int64_t *, const int *,
-                                     const float *, const int *, const float *,
-                                     const float *, float *, hipStream_t);
-extern "C" int amg_sell_relax_f32(int64_t, int64_t, const int64_t *, const int *,
-                                  const float *, const int *, const float *,
-                                  const float *, const float *, float *,
-                                  hipStream_t);
-
-// value-type dispatch for the cycle (the fp32 hierarchy of mixed precision)
-template <typename T> struct ops;
-template <> struct ops<double> {
-    static int spmv(int64_t n, int64_t nnz, const int *p, const int *c, const double *v,
-                    const double *x, double a, double b, double *y, int sw, hipStream_t s) {
-        return amg_spmv_f64(n, nnz, p, c, v, x, a, b, y, sw, s);
+// Value-type dispatch for the templated cycle (fp64, or the fp32 hierarchy of
+// mixed precision): name<T>(args...) calls amg_name_f64 or amg_name_f32 from
+// amg_kernels.h.  BSR is fp64-only (block_value + mixed precision is rejected
+// upstream); its call sites refuse T = float themselves.
+#define AMG_BY_TYPE(name)                                 \
+    template <typename T, typename... Args>               \
+    static inline int name(Args... args) {                \
+        if constexpr (std::is_same_v<T, double>)          \
+            return amg_##name##_f64(args...);             \
+        else                                              \
+            return amg_##name##_f32(args...);             \
     }
-    static int residual(int64_t n, int64_t nnz, const int *p, const int *c, const double *v,
-                        const double *rhs, const double *x, double *r, int sw,
-                        hipStream_t s) {
-        return amg_residual_f64(n, nnz, p, c, v, rhs, x, r, sw, s);
-    }
-    static int gemv(int64_t n, const double *inv, const double *f, double *u,
-                    hipStream_t s) {
-        return amg_gemv_f64(n, inv, f, u, s);
-    }
-    static int sell_spmv(int64_t n, int64_t ns, const int64_t *soff, const int *c,
-                         const double *v, const int *sr, const double *x, double a,
-                         double b, double *y, hipStream_t s) {
-        return amg_sell_spmv_f64(n, ns, soff, c, v, sr, x, a, b, y, s);
-    }
-    static int sell_residual(int64_t n, int64_t ns, const int64_t *soff, const int *c,
-                             const double *v, const int *sr, const double *rhs,
-                             const double *x, double *r, hipStream_t s) {
-        return amg_sell_residual_f64(n, ns, soff, c, v, sr, rhs, x, r, s);
-    }
-    static int sell_relax(int64_t n, int64_t ns, const int64_t *soff, const int *c,
-                          const double *v, const int *sr, const double *M,
-                          const double *rhs, const double *x, double *xn,
-                          hipStream_t s) {
-        return amg_sell_relax_f64(n, ns, soff, c, v, sr, M, rhs, x, xn, s);
-    }
-    static int axpby(int64_t n, double a, const double *x, double b, double *y,
-                     hipStream_t s) {
-        return amg_axpby_f64(n, a, x, b, y, s);
-    }
-    static int vmul(int64_t n, const double *m, const double *x, double *z,
-                    hipStream_t s) {
-        return amg_vmul_f64(n, 1.0, m, x, 0.0, z, s);
-    }
-    static int fill(int64_t n, double *x, hipStream_t s) {
-        return amg_fill_f64(n, 0.0, x, s);
-    }
-    static int bsr_spmv(int64_t nb, int bs, const int *p, const int *c,
-                        const double *v, const double *x, double a, double b,
-                        double *y, hipStream_t s) {
-        return amg_bsr_spmv_f64(nb, bs, p, c, v, x, a, b, y, s);
-    }
-    static int bsr_residual(int64_t nb, int bs, const int *p, const int *c,
-                            const double *v, const double *rhs, const double *x,
-                            double *r, hipStream_t s) {
-        return amg_bsr_residual_f64(nb, bs, p, c, v, rhs, x, r, s);
-    }
-    static int bsr_relax(int64_t nb, int bs, const int *p, const int *c,
-                         const double *v, const double *M, const double *rhs,
-                         const double *x, double *t, hipStream_t s) {
-        return amg_bsr_relax_f64(nb, bs, p, c, v, M, rhs, x, t, s);
-    }
-};
-template <> struct ops<float> {
-    static int spmv(int64_t n, int64_t nnz, const int *p, const int *c, const float *v,
-                    const float *x, double a, double b, float *y, int sw, hipStream_t s) {
-        return amg_spmv_f32(n, nnz, p, c, v, x, a, b, y, sw, s);
-    }
-    static int residual(int64_t n, int64_t nnz, const int *p, const int *c, const float *v,
-                        const float *rhs, const float *x, float *r, int sw, hipStream_t s) {
-        return amg_residual_f32(n, nnz, p, c, v, rhs, x, r, sw, s);
-    }
-    static int gemv(int64_t n, const float *inv, const float *f, float *u, hipStream_t s) {
-        return amg_gemv_f32(n, inv, f, u, s);
-    }
-    static int sell_spmv(int64_t n, int64_t ns, const int64_t *soff, const int *c,
-                         const float *v, const int *sr, const float *x, double a,
-                         double b, float *y, hipStream_t s) {
-        return amg_sell_spmv_f32(n, ns, soff, c, v, sr, x, a, b, y, s);
-    }
-    static int sell_residual(int64_t n, int64_t ns, const int64_t *soff, const int *c,
-                             const float *v, const int *sr, const float *rhs,
-                             const float *x, float *r, hipStream_t s) {
-        return amg_sell_residual_f32(n, ns, soff, c, v, sr, rhs, x, r, s);
-    }
-    static int sell_relax(int64_t n, int64_t ns, const int64_t *soff, const int *c,
-                          const float *v, const int *sr, const float *M,
-                          const float *rhs, const float *x, float *xn,
-                          hipStream_t s) {
-        return amg_sell_relax_f32(n, ns, soff, c, v, sr, M, rhs, x, xn, s);
-    }
-    static int axpby(int64_t n, double a, const float *x, double b, float *y,
-                     hipStream_t s) {
-        return amg_axpby_f32(n, a, x, b, y, s);
-    }
-    static int vmul(int64_t n, const float *m, const float *x, float *z,
-                    hipStream_t s) {
-        return amg_vmul_f32(n, 1.0, m, x, 0.0, z, s);
-    }
-    static int fill(int64_t n, float *x, hipStream_t s) {
-        return amg_fill_f32(n, 0.0, x, s);
-    }
-    // BSR is fp64-only (block_value + mixed precision is rejected upstream)
-    static int bsr_spmv(int64_t, int, const int *, const int *, const float *,
-                        const float *, double, double, float *, hipStream_t) {
-        return (int)hipErrorInvalidValue;
-    }
-    static int bsr_residual(int64_t, int, const int *, const int *, const float *,
-                            const float *, const float *, float *, hipStream_t) {
-        return (int)hipErrorInvalidValue;
-    }
-    static int bsr_relax(int64_t, int, const int *, const int *, const float *,
-                         const float *, const float *, const float *, float *,
-                         hipStream_t) {
-        return (int)hipErrorInvalidValue;
-    }
-};
+AMG_BY_TYPE(spmv)
+AMG_BY_TYPE(residual)
+AMG_BY_TYPE(gemv)
+AMG_BY_TYPE(sell_spmv)
+AMG_BY_TYPE(sell_residual)
+AMG_BY_TYPE(sell_relax)
+AMG_BY_TYPE(axpby)
+AMG_BY_TYPE(vmul)
+AMG_BY_TYPE(fill)
+#undef AMG_BY_TYPE
 
 // x_new = x + M ∘ (rhs - A x), written to a separate buffer (pointer swap)
 template <int SUBW, typename T>
@@ -226,8 +84,6 @@ __global__ void relax_zero_k(int64_t n, const T *__restrict__ M,
 static inline int nblocks_d(int64_t work, int block = 256, int cap = 2048) {
     return amg_nblocks(work, block, cap);
 }
-
-// LevelDesc moved to amg_common.h (shared with capi_gpu.hip)
 
 struct GraphEntry {
     const double *rhs;
@@ -278,15 +134,33 @@ struct Driver {
 template <typename T>
 static int level_residual(Driver *D, const LevelDesc &L, const T *rhs, const T *x,
                           T *r) {
-    if (L.bsize)
-        return ops<T>::bsr_residual(L.nbrows, L.bsize, L.bptr, L.bcol,
-                                    (const T *)L.bval, rhs, x, r, D->stream);
+    if (L.bsize) {
+        if constexpr (std::is_same_v<T, double>)
+            return amg_bsr_residual_f64(L.nbrows, L.bsize, L.bptr, L.bcol, L.bval, rhs,
+                                        x, r, D->stream);
+        else
+            return (int)hipErrorInvalidValue;
+    }
     if (L.nslice)
-        return ops<T>::sell_residual(L.nrows, L.nslice, L.soff, L.scol,
-                                     (const T *)L.sval, L.srows, rhs, x, r,
-                                     D->stream);
-    return ops<T>::residual(L.nrows, L.nnz, L.ptr, L.col, (const T *)L.val, rhs, x, r,
-                            L.subw, D->stream);
+        return sell_residual<T>(L.nrows, L.nslice, L.soff, L.scol, (const T *)L.sval,
+                                L.srows, rhs, x, r, D->stream);
+    return residual<T>(L.nrows, L.nnz, L.ptr, L.col, (const T *)L.val, rhs, x, r, L.subw,
+                       D->stream);
+}
+
+// y = P x + beta y (prolong) or y = R x + beta y, through the operator's SELL
+// image when it has one, else CSR; nrows is the row count of that operator
+template <typename T>
+static int transfer(Driver *D, const LevelDesc &L, bool prolong, int64_t nrows,
+                    const T *x, double beta, T *y) {
+    const bool p = prolong;
+    if (const int64_t nslice = p ? L.pnslice : L.rnslice)
+        return sell_spmv<T>(nrows, nslice, p ? L.psoff : L.rsoff, p ? L.pscol : L.rscol,
+                            (const T *)(p ? L.psval : L.rsval), p ? L.psrows : L.rsrows,
+                            x, 1.0, beta, y, D->stream);
+    return spmv<T>(nrows, p ? L.pnnz : L.rnnz, p ? L.pptr : L.rptr, p ? L.pcol : L.rcol,
+                   (const T *)(p ? L.pval : L.rval), x, 1.0, beta, y,
+                   p ? L.psubw : L.rsubw, D->stream);
 }
 
 // Chebyshev polynomial smoothing, in place on x (driver twin of
@@ -296,16 +170,16 @@ template <typename T>
 static int cheb_apply(Driver *D, const LevelDesc &L, const T *rhs, T *x, T *r) {
     T *d = (T *)L.cheb_d;
     CHK(level_residual<T>(D, L, rhs, x, r));
-    if (L.M) CHK(ops<T>::vmul(L.nrows, (const T *)L.M, r, r, D->stream));
+    if (L.M) CHK(vmul<T>(L.nrows, 1.0, (const T *)L.M, r, 0.0, r, D->stream));
     double rho = 1.0 / L.cheb_sigma1;
-    CHK(ops<T>::axpby(L.nrows, 1.0 / L.cheb_theta, r, 0.0, d, D->stream));
+    CHK(axpby<T>(L.nrows, 1.0 / L.cheb_theta, r, 0.0, d, D->stream));
     for (int k = 0; k < L.cheb_degree; ++k) {
-        CHK(ops<T>::axpby(L.nrows, 1.0, d, 1.0, x, D->stream));
+        CHK(axpby<T>(L.nrows, 1.0, d, 1.0, x, D->stream));
         CHK(level_residual<T>(D, L, rhs, x, r));
-        if (L.M) CHK(ops<T>::vmul(L.nrows, (const T *)L.M, r, r, D->stream));
+        if (L.M) CHK(vmul<T>(L.nrows, 1.0, (const T *)L.M, r, 0.0, r, D->stream));
         double rho_next = 1.0 / (2.0 * L.cheb_sigma1 - rho);
-        CHK(ops<T>::axpby(L.nrows, 2.0 * rho_next / L.cheb_delta, r, rho_next * rho,
-                          d, D->stream));
+        CHK(axpby<T>(L.nrows, 2.0 * rho_next / L.cheb_delta, r, rho_next * rho, d,
+                     D->stream));
         rho = rho_next;
     }
     return 0;
@@ -360,20 +234,19 @@ static int relax_swap(Driver *D, const LevelDesc &L, const T *rhs, T **x, T **xn
     }
     if (L.bsize) {
         // xn = M o (rhs - A x); xn += x; swap
-        CHK(ops<T>::bsr_relax(L.nbrows, L.bsize, L.bptr, L.bcol, (const T *)L.bval,
-                              (const T *)L.M, rhs, *x, *xn, D->stream));
-        CHK(ops<T>::axpby(L.nrows, 1.0, *x, 1.0, *xn, D->stream));
-        T *tmp = *x;
-        *x = *xn;
-        *xn = tmp;
+        if constexpr (std::is_same_v<T, double>)
+            CHK(amg_bsr_relax_f64(L.nbrows, L.bsize, L.bptr, L.bcol, L.bval, L.M, rhs,
+                                  *x, *xn, D->stream));
+        else
+            return (int)hipErrorInvalidValue;
+        CHK(axpby<T>(L.nrows, 1.0, *x, 1.0, *xn, D->stream));
+        std::swap(*x, *xn);
         return 0;
     }
     if (L.nslice) {
-        CHK(ops<T>::sell_relax(L.nrows, L.nslice, L.soff, L.scol, (const T *)L.sval,
-                               L.srows, (const T *)L.M, rhs, *x, *xn, D->stream));
-        T *tmp = *x;
-        *x = *xn;
-        *xn = tmp;
+        CHK(sell_relax<T>(L.nrows, L.nslice, L.soff, L.scol, (const T *)L.sval, L.srows,
+                          (const T *)L.M, rhs, *x, *xn, D->stream));
+        std::swap(*x, *xn);
         return 0;
     }
     int subw = L.subw;
@@ -390,9 +263,7 @@ static int relax_swap(Driver *D, const LevelDesc &L, const T *rhs, T **x, T **xn
         default: return hipErrorInvalidValue;
     }
 #undef RCASE
-    T *tmp = *x;
-    *x = *xn;
-    *xn = tmp;
+    std::swap(*x, *xn);
     return (int)hipGetLastError();
 }
 
@@ -408,20 +279,18 @@ static int cycle(Driver *D, int li, const T *f, T **u_io, T **scratch, bool u_is
     auto relax_zero = [&](LevelDesc &LL, const T *ff, T **u2, T **sc) -> int {
         if (LL.cheb_degree || LL.bsize || LL.ilu_iters) {
             // no fused zero-guess form for these smoothers: clear + general
-            CHK(ops<T>::fill(LL.nrows, *u2, D->stream));
+            CHK(fill<T>(LL.nrows, 0.0, *u2, D->stream));
             return relax_swap<T>(D, LL, ff, u2, sc);
         }
         relax_zero_k<T><<<nblocks_d(LL.nrows), 256, 0, D->stream>>>(
             LL.nrows, (const T *)LL.M, ff, *sc);
-        T *tmp = *u2;
-        *u2 = *sc;
-        *sc = tmp;
+        std::swap(*u2, *sc);
         return 0;
     };
 
     if (coarsest) {
         if (D->coarse_inv) {
-            CHK(ops<T>::gemv(L.nrows, (const T *)D->coarse_inv, f, *u_io, D->stream));
+            CHK(gemv<T>(L.nrows, (const T *)D->coarse_inv, f, *u_io, D->stream));
         } else {
             for (int i = 0; i < D->npre + D->npost; ++i) {
                 if (u_is_zero && i == 0) {
@@ -444,12 +313,7 @@ static int cycle(Driver *D, int li, const T *f, T **u_io, T **scratch, bool u_is
     }
     // t = f - A u ; f_next = R t
     CHK(level_residual<T>(D, L, f, *u_io, *scratch));
-    if (L.rnslice)
-        CHK(ops<T>::sell_spmv(N.nrows, L.rnslice, L.rsoff, L.rscol, (const T *)L.rsval,
-                              L.rsrows, *scratch, 1.0, 0.0, (T *)N.f, D->stream));
-    else
-        CHK(ops<T>::spmv(N.nrows, L.rnnz, L.rptr, L.rcol, (const T *)L.rval, *scratch,
-                         1.0, 0.0, (T *)N.f, L.rsubw, D->stream));
+    CHK(transfer<T>(D, L, /*prolong=*/false, N.nrows, *scratch, 0.0, (T *)N.f));
     T *nu = (T *)N.u;
     T *nscratch = (T *)N.t;
     for (int c = 0; c < D->ncycle; ++c) {
@@ -457,12 +321,7 @@ static int cycle(Driver *D, int li, const T *f, T **u_io, T **scratch, bool u_is
         // after the first sub-cycle the iterate is nonzero
     }
     // u += P u_next
-    if (L.pnslice)
-        CHK(ops<T>::sell_spmv(L.nrows, L.pnslice, L.psoff, L.pscol, (const T *)L.psval,
-                              L.psrows, nu, 1.0, 1.0, *u_io, D->stream));
-    else
-        CHK(ops<T>::spmv(L.nrows, L.pnnz, L.pptr, L.pcol, (const T *)L.pval, nu, 1.0,
-                         1.0, *u_io, L.psubw, D->stream));
+    CHK(transfer<T>(D, L, /*prolong=*/true, L.nrows, nu, 1.0, *u_io));
     for (int i = 0; i < D->npost; ++i)
         CHK(relax_swap<T>(D, L, f, u_io, scratch));
     return (int)hipGetLastError();
@@ -610,65 +469,115 @@ extern "C" void amg_driver_destroy(void *h) {
     delete D;
 }
 
+// LevelDesc layout as compiled, for the ctypes twin (backend/native.py
+// LevelDescC) to check itself against when it binds
+extern "C" int amg_leveldesc_size() { return (int)sizeof(LevelDesc); }
+extern "C" int amg_leveldesc_last_offset() { return (int)offsetof(LevelDesc, ilu_b); }
+
+// The single exit of every entry point once enter_driver has succeeded; rc
+// is what the body returned (0, a failed launch, a BiCGStab breakdown).  The
+// caller's stream is always ordered after the internal one, and a solve also
+// waits for the internal stream, so no kernel is left running on the caller's
+// buffers behind an error return.  The body's code comes first.
+static int finish(Driver *D, int rc, bool sync) {
+    int rc_leave = leave_driver(D);
+    int rc_sync = sync ? (int)hipStreamSynchronize(D->stream) : 0;
+    return rc ? rc : rc_leave ? rc_leave : rc_sync;
+}
+
 // standalone preconditioner application (used by the distributed layer:
 // the Krylov loop stays in Python for halo exchange, but each local V-cycle
 // runs natively)
 extern "C" int amg_driver_precond(void *h, const double *rhs, double *x, double *x_swap) {
     Driver *D = (Driver *)h;
     CHK(enter_driver(D));
-    CHK(precond_apply_graphed(D, rhs, x, x_swap));
-    return leave_driver(D);
+    return finish(D, precond_apply_graphed(D, rhs, x, x_swap), /*sync=*/false);
+}
+
+// The fp64 fine operator the Krylov loops iterate with: level 0, or in mixed
+// mode the a64_* CSR copy (level 0 then describes the fp32 operator the cycle
+// runs on, which has no fp64 SELL or BSR image)
+struct FineOp {
+    Driver *D;
+    LevelDesc L;
+    explicit FineOp(Driver *D) : D(D), L(D->lv[0]) {
+        if (!D->f32) return;
+        L.nnz = D->a64_nnz;
+        L.ptr = D->a64_ptr;
+        L.col = D->a64_col;
+        L.val = D->a64_val;
+        L.subw = D->a64_subw;
+        L.nslice = 0;
+        L.bsize = 0;
+    }
+    // y = alpha A x + beta y, storage precedence as in level_residual
+    int spmv(const double *x, double alpha, double beta, double *y) const {
+        if (L.bsize)
+            return amg_bsr_spmv_f64(L.nbrows, L.bsize, L.bptr, L.bcol, L.bval, x, alpha,
+                                    beta, y, D->stream);
+        if (L.nslice)
+            return amg_sell_spmv_f64(L.nrows, L.nslice, L.soff, L.scol,
+                                     (const double *)L.sval, L.srows, x, alpha, beta, y,
+                                     D->stream);
+        return amg_spmv_f64(L.nrows, L.nnz, L.ptr, L.col, L.val, x, alpha, beta, y,
+                            L.subw, D->stream);
+    }
+    int residual(const double *rhs, const double *x, double *r) const {
+        return level_residual<double>(D, L, rhs, x, r);
+    }
+};
+
+struct Krylov {
+    double norm_rhs, eps, res;  // ||rhs||, absolute target, current ||r||
+};
+
+// Shared entry of the Krylov loops: ||rhs||, eps, r = rhs - A x (copied to
+// r_copy if given: BiCGStab's shadow residual) and ||r||.  A zero rhs is
+// solved by x = 0: res = eps = 0 then keeps the caller's loop from starting.
+static int krylov_begin(Driver *D, const FineOp &A, const double *rhs, double *x,
+                        double *r, double *r_copy, double tol, double abstol,
+                        Krylov *k) {
+    const int64_t n = A.L.nrows;
+    hipStream_t st = D->stream;
+    double dot;
+    CHK(amg_dot_f64(n, rhs, rhs, D->dotbuf_d, st));
+    CHK(read_dots(D, 1, &dot));
+    k->norm_rhs = sqrt(dot);
+    k->eps = k->res = 0.0;
+    if (k->norm_rhs == 0.0) return amg_fill_f64(n, 0.0, x, st);
+    k->eps = tol * k->norm_rhs > abstol ? tol * k->norm_rhs : abstol;
+    CHK(A.residual(rhs, x, r));
+    if (r_copy)
+        CHK(hipMemcpyAsync(r_copy, r, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    CHK(amg_dot_f64(n, r, r, D->dotbuf_d, st));
+    CHK(read_dots(D, 1, &dot));
+    k->res = sqrt(dot);
+    return 0;
+}
+
+// shared tail: iteration count and relative residual (0 for a zero rhs)
+static int krylov_end(const Krylov &k, int64_t iter, int64_t *iters_out,
+                      double *resid_out) {
+    *iters_out = iter;
+    *resid_out = k.norm_rhs == 0.0 ? 0.0 : k.res / k.norm_rhs;
+    return 0;
 }
 
 // Preconditioned CG (parity: amgcl/solver/cg.hpp:152-204).
 // Work vectors r,s,p,q + s_swap provided by the caller (device, n doubles).
-extern "C" int amg_driver_cg(void *h, const double *rhs, double *x, double *r, double *s,
-                             double *p, double *q, double *s_swap, double tol,
-                             double abstol, int maxiter, int64_t *iters_out,
-                             double *resid_out) {
-    Driver *D = (Driver *)h;
-    CHK(enter_driver(D));
-    const LevelDesc &L0 = D->lv[0];
-    const int64_t n = L0.nrows;
-    // the Krylov loop always iterates with the fp64 fine operator (in mixed
-    // mode L0's LevelDesc holds the fp32 copy used inside the cycle)
-    const int64_t knnz = D->f32 ? D->a64_nnz : L0.nnz;
-    const int *kptr = D->f32 ? D->a64_ptr : L0.ptr;
-    const int *kcol = D->f32 ? D->a64_col : L0.col;
-    const double *kval = D->f32 ? D->a64_val : (const double *)L0.val;
-    const int ksubw = D->f32 ? D->a64_subw : L0.subw;
-    const int64_t ksell = D->f32 ? 0 : L0.nslice;  // fp64 SELL fine operator
-    const int kbsr = D->f32 ? 0 : L0.bsize;        // fp64 BSR fine operator
+static int cg_solve(Driver *D, const double *rhs, double *x, double *r, double *s,
+                    double *p, double *q, double *s_swap, double tol, double abstol,
+                    int maxiter, int64_t *iters_out, double *resid_out) {
+    const FineOp A(D);
+    const int64_t n = A.L.nrows;
     hipStream_t st = D->stream;
     double dots[2];
-
-    CHK(amg_dot_f64(n, rhs, rhs, D->dotbuf_d, st));
-    CHK(read_dots(D, 1, dots));
-    double norm_rhs = sqrt(dots[0]);
-    if (norm_rhs == 0.0) {
-        CHK(amg_fill_f64(n, 0.0, x, st));
-        *iters_out = 0;
-        *resid_out = 0.0;
-        CHK(leave_driver(D));
-        return hipStreamSynchronize(st);
-    }
-    double eps = tol * norm_rhs > abstol ? tol * norm_rhs : abstol;
-
-    if (kbsr)
-        CHK(amg_bsr_residual_f64(L0.nbrows, kbsr, L0.bptr, L0.bcol,
-                                 (const double *)L0.bval, rhs, x, r, st));
-    else if (ksell)
-        CHK(amg_sell_residual_f64(n, ksell, L0.soff, L0.scol, (const double *)L0.sval,
-                                  L0.srows, rhs, x, r, st));
-    else
-        CHK(amg_residual_f64(n, knnz, kptr, kcol, kval, rhs, x, r, ksubw, st));
-    CHK(amg_dot_f64(n, r, r, D->dotbuf_d, st));
-    CHK(read_dots(D, 1, dots));
-    double res = sqrt(dots[0]);
+    Krylov k;
+    CHK(krylov_begin(D, A, rhs, x, r, nullptr, tol, abstol, &k));
 
     double rho1 = 0.0, rho2 = 0.0;
     int64_t iter = 0;
-    while (res > eps && iter < maxiter) {
+    while (k.res > k.eps && iter < maxiter) {
         CHK(precond_apply_graphed(D, r, s, s_swap));
         rho2 = rho1;
         CHK(amg_dot_f64(n, r, s, D->dotbuf_d, st));
@@ -679,82 +588,47 @@ extern "C" int amg_driver_cg(void *h, const double *rhs, double *x, double *r, d
         } else {
             CHK(amg_axpby_f64(n, 1.0, s, rho1 / rho2, p, st));
         }
-        if (kbsr)
-            CHK(amg_bsr_spmv_f64(L0.nbrows, kbsr, L0.bptr, L0.bcol,
-                                 (const double *)L0.bval, p, 1.0, 0.0, q, st));
-        else if (ksell)
-            CHK(amg_sell_spmv_f64(n, ksell, L0.soff, L0.scol, (const double *)L0.sval,
-                                  L0.srows, p, 1.0, 0.0, q, st));
-        else
-            CHK(amg_spmv_f64(n, knnz, kptr, kcol, kval, p, 1.0, 0.0, q, ksubw, st));
+        CHK(A.spmv(p, 1.0, 0.0, q));
         CHK(amg_dot_f64(n, q, p, D->dotbuf_d, st));
         CHK(read_dots(D, 1, dots));
         double alpha = rho1 / dots[0];
         // fused x/r update + residual norm (single pass over x,r,p,q)
         CHK(amg_cg_tail_f64(n, alpha, p, q, x, r, D->dotbuf_d, st));
         CHK(read_dots(D, 1, dots));
-        res = sqrt(dots[0]);
+        k.res = sqrt(dots[0]);
         ++iter;
     }
-    *iters_out = iter;
-    *resid_out = res / norm_rhs;
-    CHK(leave_driver(D));
-    return hipStreamSynchronize(st);
+    return krylov_end(k, iter, iters_out, resid_out);
+}
+
+extern "C" int amg_driver_cg(void *h, const double *rhs, double *x, double *r, double *s,
+                             double *p, double *q, double *s_swap, double tol,
+                             double abstol, int maxiter, int64_t *iters_out,
+                             double *resid_out) {
+    Driver *D = (Driver *)h;
+    CHK(enter_driver(D));
+    return finish(D, cg_solve(D, rhs, x, r, s, p, q, s_swap, tol, abstol, maxiter,
+                              iters_out, resid_out), /*sync=*/true);
 }
 
 // Preconditioned BiCGStab, right-preconditioned
 // (parity: amgcl/solver/bicgstab.hpp:176-240).
-// work: r,p,v,s2,t2,rh,T,T_swap (device, n doubles each)
-extern "C" int amg_driver_bicgstab(void *h, const double *rhs, double *x, double *r,
-                                   double *p, double *v, double *s2, double *t2,
-                                   double *rh, double *T, double *T_swap, double tol,
-                                   double abstol, int maxiter, int64_t *iters_out,
-                                   double *resid_out) {
-    Driver *D = (Driver *)h;
-    CHK(enter_driver(D));
-    const LevelDesc &L0 = D->lv[0];
-    const int64_t n = L0.nrows;
-    // the Krylov loop always iterates with the fp64 fine operator (in mixed
-    // mode L0's LevelDesc holds the fp32 copy used inside the cycle)
-    const int64_t knnz = D->f32 ? D->a64_nnz : L0.nnz;
-    const int *kptr = D->f32 ? D->a64_ptr : L0.ptr;
-    const int *kcol = D->f32 ? D->a64_col : L0.col;
-    const double *kval = D->f32 ? D->a64_val : (const double *)L0.val;
-    const int ksubw = D->f32 ? D->a64_subw : L0.subw;
-    const int64_t ksell = D->f32 ? 0 : L0.nslice;  // fp64 SELL fine operator
-    const int kbsr = D->f32 ? 0 : L0.bsize;        // fp64 BSR fine operator
+// work: r,p,v,s2,t2,rh,T,T_swap (device, n doubles each); -2 = breakdown
+static int bicgstab_solve(Driver *D, const double *rhs, double *x, double *r, double *p,
+                          double *v, double *s2, double *t2, double *rh, double *T,
+                          double *T_swap, double tol, double abstol, int maxiter,
+                          int64_t *iters_out, double *resid_out) {
+    const FineOp A(D);
+    const int64_t n = A.L.nrows;
     hipStream_t st = D->stream;
     double dots[2];
-
-    CHK(amg_dot_f64(n, rhs, rhs, D->dotbuf_d, st));
-    CHK(read_dots(D, 1, dots));
-    double norm_rhs = sqrt(dots[0]);
-    if (norm_rhs == 0.0) {
-        CHK(amg_fill_f64(n, 0.0, x, st));
-        *iters_out = 0;
-        *resid_out = 0.0;
-        CHK(leave_driver(D));
-        return hipStreamSynchronize(st);
-    }
-    double eps = tol * norm_rhs > abstol ? tol * norm_rhs : abstol;
-
-    if (kbsr)
-        CHK(amg_bsr_residual_f64(L0.nbrows, kbsr, L0.bptr, L0.bcol,
-                                 (const double *)L0.bval, rhs, x, r, st));
-    else if (ksell)
-        CHK(amg_sell_residual_f64(n, ksell, L0.soff, L0.scol, (const double *)L0.sval,
-                                  L0.srows, rhs, x, r, st));
-    else
-        CHK(amg_residual_f64(n, knnz, kptr, kcol, kval, rhs, x, r, ksubw, st));
-    CHK(hipMemcpyAsync(rh, r, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    CHK(amg_dot_f64(n, r, r, D->dotbuf_d, st));
-    CHK(read_dots(D, 1, dots));
-    double res = sqrt(dots[0]);
+    Krylov k;
+    CHK(krylov_begin(D, A, rhs, x, r, rh, tol, abstol, &k));
 
     double rho1 = 0.0, rho2 = 0.0, alpha = 0.0, omega = 0.0;
     int64_t iter = 0;
     bool first = true;
-    while (res > eps && iter < maxiter) {
+    while (k.res > k.eps && iter < maxiter) {
         rho2 = rho1;
         CHK(amg_dot_f64(n, r, rh, D->dotbuf_d, st));
         CHK(read_dots(D, 1, dots));
@@ -769,14 +643,7 @@ extern "C" int amg_driver_bicgstab(void *h, const double *rhs, double *x, double
         }
         // v = A (M^-1 p);  T = M^-1 p
         CHK(precond_apply_graphed(D, p, T, T_swap));
-        if (kbsr)
-            CHK(amg_bsr_spmv_f64(L0.nbrows, kbsr, L0.bptr, L0.bcol,
-                                 (const double *)L0.bval, T, 1.0, 0.0, v, st));
-        else if (ksell)
-            CHK(amg_sell_spmv_f64(n, ksell, L0.soff, L0.scol, (const double *)L0.sval,
-                                  L0.srows, T, 1.0, 0.0, v, st));
-        else
-            CHK(amg_spmv_f64(n, knnz, kptr, kcol, kval, T, 1.0, 0.0, v, ksubw, st));
+        CHK(A.spmv(T, 1.0, 0.0, v));
         CHK(amg_dot_f64(n, rh, v, D->dotbuf_d, st));
         CHK(read_dots(D, 1, dots));
         alpha = rho1 / dots[0];
@@ -784,18 +651,10 @@ extern "C" int amg_driver_bicgstab(void *h, const double *rhs, double *x, double
         CHK(amg_axpbypcz_f64(n, 1.0, r, -alpha, v, 0.0, s2, st));
         CHK(amg_dot_f64(n, s2, s2, D->dotbuf_d, st));
         CHK(read_dots(D, 1, dots));
-        res = sqrt(dots[0]);
-        if (res > eps) {
+        k.res = sqrt(dots[0]);
+        if (k.res > k.eps) {
             CHK(precond_apply_graphed(D, s2, T, T_swap));
-            if (kbsr)
-                CHK(amg_bsr_spmv_f64(L0.nbrows, kbsr, L0.bptr, L0.bcol,
-                                     (const double *)L0.bval, T, 1.0, 0.0, t2, st));
-            else if (ksell)
-                CHK(amg_sell_spmv_f64(n, ksell, L0.soff, L0.scol,
-                                      (const double *)L0.sval, L0.srows, T, 1.0, 0.0,
-                                      t2, st));
-            else
-                CHK(amg_spmv_f64(n, knnz, kptr, kcol, kval, T, 1.0, 0.0, t2, ksubw, st));
+            CHK(A.spmv(T, 1.0, 0.0, t2));
             CHK(amg_dot2_f64(n, t2, s2, t2, t2, D->dotbuf_d, st));
             CHK(read_dots(D, 2, dots));
             omega = dots[0] / dots[1];
@@ -804,12 +663,21 @@ extern "C" int amg_driver_bicgstab(void *h, const double *rhs, double *x, double
             CHK(amg_axpbypcz_f64(n, 1.0, s2, -omega, t2, 0.0, r, st));
             CHK(amg_dot_f64(n, r, r, D->dotbuf_d, st));
             CHK(read_dots(D, 1, dots));
-            res = sqrt(dots[0]);
+            k.res = sqrt(dots[0]);
         }
         ++iter;
     }
-    *iters_out = iter;
-    *resid_out = res / norm_rhs;
-    CHK(leave_driver(D));
-    return hipStreamSynchronize(st);
+    return krylov_end(k, iter, iters_out, resid_out);
+}
+
+extern "C" int amg_driver_bicgstab(void *h, const double *rhs, double *x, double *r,
+                                   double *p, double *v, double *s2, double *t2,
+                                   double *rh, double *T, double *T_swap, double tol,
+                                   double abstol, int maxiter, int64_t *iters_out,
+                                   double *resid_out) {
+    Driver *D = (Driver *)h;
+    CHK(enter_driver(D));
+    return finish(D, bicgstab_solve(D, rhs, x, r, p, v, s2, t2, rh, T, T_swap, tol,
+                                    abstol, maxiter, iters_out, resid_out),
+                  /*sync=*/true);
 }

@@ -17,6 +17,7 @@
 #include <cstdio>
 
 #include "amg_common.h"
+#include "amg_kernels.h"
 
 static inline int nblocks(int64_t work, int block = 256, int cap = 2048) {
     return amg_nblocks(work, block, cap);

@@ -24,6 +24,8 @@
 
 #include <cstdint>
 
+#include "amg_kernels.h"
+
 #define WAVE 64
 
 static inline int nblk(int64_t work, int block = 256, int cap = 4096) {

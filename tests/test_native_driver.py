@@ -223,6 +223,93 @@ def test_native_driver_bsr_levels(hip):
     assert np.linalg.norm(bh - Ah @ xh) / np.linalg.norm(bh) < 1e-5
 
 
+def _storage_case(storage, solver):
+    """(A, b, prm, tol) for one fine-operator storage of the Krylov loop."""
+    if storage == "bsr":
+        from amgcl_amd.generators import elasticity3d, rigid_body_modes
+
+        A, b, coords = elasticity3d(12)
+        precond = {"class": "amg", "block_value": 3, "keep_host_matrices": True,
+                   "relax": {"type": "chebyshev"},
+                   "coarsening": {"type": "smoothed_aggregation",
+                                  "nullspace_raw": rigid_body_modes(coords),
+                                  "block_size": 3,
+                                  "estimate_spectral_radius": True,
+                                  "power_iters": 10}}
+        tol, maxiter = 1e-6, 300
+    else:
+        A, b = am.poisson3d(24, rhs="random")
+        precond = {"class": "amg", "coarse_enough": 300}
+        if storage == "sell":
+            precond.update({"sell": "auto", "sell_min_rows": 1,
+                            "sell_min_mean": 0.0})
+        elif storage == "mixed":
+            precond = {"class": "amg", "precision": "mixed"}
+        tol, maxiter = 1e-8, 100
+    prm = {"precond": precond,
+           "solver": {"type": solver, "tol": tol, "maxiter": maxiter}}
+    return A, b, prm, tol
+
+
+@pytest.mark.parametrize("storage", ["csr", "sell", "bsr", "mixed"])
+@pytest.mark.parametrize("solver", ["cg", "bicgstab"])
+def test_native_storage_matrix(hip, solver, storage):
+    """Both native Krylov loops against the generic path for every storage
+    the fine operator can carry (CSR, SELL, BSR, fp64 override of a mixed
+    hierarchy)."""
+    from amgcl_amd.backend.hip import DeviceBSR
+
+    A, b, prm, tol = _storage_case(storage, solver)
+    s = am.make_solver(A, prm, backend=hip)
+    assert s._native is not None, "native driver should engage for this config"
+    A0 = s.P.levels[0].A
+    assert isinstance(A0, DeviceBSR) == (storage == "bsr")
+    assert bool(getattr(A0, "nslice", 0)) == (storage == "sell")
+    assert s._native._mixed == (storage == "mixed")
+    x1, it1, res1 = s(b)
+
+    s._native = None  # generic path on the same hierarchy
+    x2, it2, res2 = s(b)
+    r = b - A @ hip.to_host(x1)
+    true = np.linalg.norm(r) / np.linalg.norm(b)
+    print(f"storage_matrix {solver}/{storage}: native {it1} it {res1:.3e}, "
+          f"generic {it2} it {res2:.3e}, true {true:.3e}")
+    if solver == "cg":
+        # the native CG fuses the x/r update (cg_tail): last-bit differences
+        assert abs(it1 - it2) <= 1, (it1, it2)
+    else:
+        assert it1 == it2
+    assert res1 < tol and res2 < tol
+    assert true < 10 * tol
+
+
+@pytest.mark.parametrize("solver", ["cg", "bicgstab"])
+def test_native_zero_rhs(hip, solver):
+    """b = 0 takes the driver's shortcut: x is cleared, nothing iterates."""
+    import torch
+
+    A, _ = am.poisson3d(16)
+    s = am.make_solver(A, {"solver": {"type": solver, "tol": 1e-8, "maxiter": 100}},
+                       backend=hip)
+    assert s._native is not None
+    x0 = hip.from_host(np.ones(A.nrows))
+    x, iters, resid = s(np.zeros(A.nrows), x=x0)
+    assert iters == 0 and resid == 0.0
+    assert x is x0 and torch.count_nonzero(x).item() == 0
+
+
+def test_leveldesc_layout():
+    """The ctypes LevelDescC and the compiled LevelDesc agree on the struct's
+    size and on the offset of its last field (what _bind() enforces)."""
+    import ctypes
+
+    from amgcl_amd.backend import native
+
+    L = native._bind()
+    assert L.amg_leveldesc_size() == ctypes.sizeof(native.LevelDescC)
+    assert L.amg_leveldesc_last_offset() == native.LevelDescC.ilu_b.offset
+
+
 @pytest.mark.gpu
 def test_block_ilu0_on_hip():
     """block_ilu0 smoothing on the HIP backend: BSR L/U iterated-Jacobi
