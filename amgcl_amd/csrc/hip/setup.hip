@@ -810,6 +810,36 @@ __global__ void spgemm_ub_k(int64_t an, const int *__restrict__ aptr,
     }
 }
 
+// Small-bin rows work in chunks of SGRP A entries: each lane of the 8-lane
+// group stages ONE A entry (its B-row begin and length, loaded in parallel).
+// The count pass, whose result does not depend on insertion order, then
+// flattens the chunk's products: a width-8 scan gives the product prefix and
+// the lanes stride the products t = lane, lane+8, ...  Everything stays in
+// registers; all shuffles sit in group-uniform control flow.
+__device__ __forceinline__ int sg_scan(int x, int lane) {
+#pragma unroll
+    for (int d = 1; d < SGRP; d <<= 1) {
+        int v = __shfl_up(x, d, SGRP);
+        if (lane >= d) x += v;
+    }
+    return x;  // inclusive
+}
+
+// entry holding product t of the chunk: the number of inclusive prefixes
+// <= t (empty B rows repeat a prefix and are stepped over); `e` receives
+// that entry's exclusive prefix. t >= p[SGRP-1] clamps to the last lane.
+__device__ __forceinline__ int sg_find(const int (&p)[SGRP], int t, int &e) {
+    int ja = 0;
+    e = 0;
+#pragma unroll
+    for (int k = 0; k < SGRP - 1; ++k)
+        if (p[k] <= t) {
+            ja = k + 1;
+            e = p[k];
+        }
+    return ja;
+}
+
 // templated on the LDS table size, tiered by ub: the dominant fine-level
 // A*P rows have <= 24 candidates, where a 32-slot table quarters the
 // init/extract traffic of the 128-slot one (measured: the init dominates
@@ -835,16 +865,33 @@ __global__ void spgemm_count_small_k(int64_t an, const int *__restrict__ aptr,
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_wave_barrier();
         int inserted = 0;
-        for (int ja = aptr[row]; ja < aptr[row + 1]; ++ja) {
-            int ca = acol[ja];
-            for (int jb = bptr[ca] + lane; jb < bptr[ca + 1]; jb += SGRP) {
-                int key = bcol[jb];
-                uint32_t h = ((uint32_t)key * 2654435761u) & MASK;
-                while (true) {
-                    int old = atomicCAS(&tk[h], -1, key);
-                    if (old == -1) { ++inserted; break; }
-                    if (old == key) break;
-                    h = (h + 1) & MASK;
+        const int aend = aptr[row + 1];
+        for (int j0 = aptr[row]; j0 < aend; j0 += SGRP) {
+            int j = j0 + lane;
+            int bb = 0, bl = 0;
+            if (j < aend) {
+                int ca = acol[j];
+                bb = bptr[ca];
+                bl = bptr[ca + 1] - bb;
+            }
+            int inc = sg_scan(bl, lane);
+            int p[SGRP];
+#pragma unroll
+            for (int k = 0; k < SGRP; ++k) p[k] = __shfl(inc, k, SGRP);
+            const int tot = p[SGRP - 1];
+            for (int t0 = 0; t0 < tot; t0 += SGRP) {
+                int t = t0 + lane, e;
+                int ja = sg_find(p, t, e);
+                int bj = __shfl(bb, ja, SGRP);
+                if (t < tot) {
+                    int key = bcol[bj + (t - e)];
+                    uint32_t h = ((uint32_t)key * 2654435761u) & MASK;
+                    while (true) {
+                        int old = atomicCAS(&tk[h], -1, key);
+                        if (old == -1) { ++inserted; break; }
+                        if (old == key) break;
+                        h = (h + 1) & MASK;
+                    }
                 }
             }
         }
@@ -890,20 +937,39 @@ __global__ void spgemm_fill_small_k(int64_t an, const int *__restrict__ aptr,
         }
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_wave_barrier();
-        for (int ja = aptr[row]; ja < aptr[row + 1]; ++ja) {
-            int ca = acol[ja];
-            double va = aval[ja];
-            for (int jb = bptr[ca] + lane; jb < bptr[ca + 1]; jb += SGRP) {
-                int key = bcol[jb];
-                double v = va * bval[jb];
-                uint32_t h = ((uint32_t)key * 2654435761u) & SMASK_S;
-                while (true) {
-                    int old = atomicCAS(&tk[h], -1, key);
-                    if (old == -1 || old == key) {
-                        atomicAdd(&tv[h], v);
-                        break;
+        const int aend = aptr[row + 1];
+        for (int j0 = aptr[row]; j0 < aend; j0 += SGRP) {
+            int j = j0 + lane;
+            int bb = 0, bl = 0;
+            double va = 0.0;
+            if (j < aend) {
+                int ca = acol[j];
+                va = aval[j];
+                bb = bptr[ca];
+                bl = bptr[ca + 1] - bb;
+            }
+            // The entries are staged in parallel, but inserted one after the
+            // other with the lanes striding one B row, as before: the slot a
+            // key lands in, and with it the order of an unsorted row and the
+            // order of every sum, depend on which products share an
+            // instruction, and results must not move with this change.
+            const int nj = min(SGRP, aend - j0);
+            for (int k = 0; k < nj; ++k) {
+                const int bk = __shfl(bb, k, SGRP);
+                const int ek = bk + __shfl(bl, k, SGRP);
+                const double vk = __shfl(va, k, SGRP);
+                for (int jb = bk + lane; jb < ek; jb += SGRP) {
+                    int key = bcol[jb];
+                    double v = vk * bval[jb];
+                    uint32_t h = ((uint32_t)key * 2654435761u) & SMASK_S;
+                    while (true) {
+                        int old = atomicCAS(&tk[h], -1, key);
+                        if (old == -1 || old == key) {
+                            atomicAdd(&tv[h], v);
+                            break;
+                        }
+                        h = (h + 1) & SMASK_S;
                     }
-                    h = (h + 1) & SMASK_S;
                 }
             }
         }
@@ -960,6 +1026,16 @@ __device__ __forceinline__ int pfx_find(const int *pfx, int len, int t) {
     return lo;
 }
 
+// inclusive wave scan of the staged B-row lengths
+__device__ __forceinline__ int wave_scan(int x, int lane) {
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        int v = __shfl_up(x, d, WAVE);
+        if (lane >= d) x += v;
+    }
+    return x;
+}
+
 // Count pass, wave per row, templated on the LDS table size. The exact
 // output length is unknown before counting, so rows tier by the product
 // upper bound: distinct keys <= ub, so any row with ub < SLOTS is safe in
@@ -1013,16 +1089,26 @@ __global__ void spgemm_count_k(int64_t an, const int *__restrict__ biglist,
         int ab = aptr[row], alen = aptr[row + 1] - ab;
         for (int t = lane; t < SLOTS; t += WAVE) tk[t] = -1;
         const bool huge = alen > BIGROW;
-        if (!huge && lane == 0) {
-            // product-space prefix (serial scan by lane 0)
+        if (!huge) {
+            // product-space prefix: every lane stages its own A entries,
+            // wave scan per 64-wide chunk, running total carried across
             int acc = 0;
-            for (int j = 0; j < alen; ++j) {
-                pfx[wid][j] = acc;
-                int ca = acol[ab + j];
-                bbeg[wid][j] = bptr[ca];
-                acc += bptr[ca + 1] - bptr[ca];
+            for (int j0 = 0; j0 < alen; j0 += WAVE) {
+                int j = j0 + lane;
+                int bb = 0, bl = 0;
+                if (j < alen) {
+                    int ca = acol[ab + j];
+                    bb = bptr[ca];
+                    bl = bptr[ca + 1] - bb;
+                }
+                int inc = wave_scan(bl, lane);
+                if (j < alen) {
+                    pfx[wid][j] = acc + inc - bl;
+                    bbeg[wid][j] = bb;
+                }
+                acc += __shfl(inc, WAVE - 1, WAVE);
             }
-            pfx[wid][alen] = acc;
+            if (lane == 0) pfx[wid][alen] = acc;
         }
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_wave_barrier();
@@ -1116,17 +1202,24 @@ __global__ void spgemm_fill_k(int64_t an, const int *__restrict__ biglist,
             tv[t] = 0.0;
         }
         if (!huge) {
-            for (int j = lane; j < alen; j += WAVE) av[wid][j] = aval[ab + j];
-            if (lane == 0) {
-                int acc = 0;
-                for (int j = 0; j < alen; ++j) {
-                    pfx[wid][j] = acc;
+            int acc = 0;
+            for (int j0 = 0; j0 < alen; j0 += WAVE) {
+                int j = j0 + lane;
+                int bb = 0, bl = 0;
+                if (j < alen) {
                     int ca = acol[ab + j];
-                    bbeg[wid][j] = bptr[ca];
-                    acc += bptr[ca + 1] - bptr[ca];
+                    av[wid][j] = aval[ab + j];
+                    bb = bptr[ca];
+                    bl = bptr[ca + 1] - bb;
                 }
-                pfx[wid][alen] = acc;
+                int inc = wave_scan(bl, lane);
+                if (j < alen) {
+                    pfx[wid][j] = acc + inc - bl;
+                    bbeg[wid][j] = bb;
+                }
+                acc += __shfl(inc, WAVE - 1, WAVE);
             }
+            if (lane == 0) pfx[wid][alen] = acc;
         }
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_wave_barrier();
