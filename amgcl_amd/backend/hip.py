@@ -62,7 +62,7 @@ class DeviceCSR:
             b += self.sval.numel() * self.sval.element_size()
         return b
 
-    def build_sell(self, sigma=0):
+    def build_sell(self, sigma=0, sigma_min_rows=1 << 16, sigma_min_pad=1.08):
         """Build the SELL-64 image of this matrix (kernels.hip rationale:
         wave-native layout; lane = row, slices column-major).  The CSR arrays
         are kept — transfers and non-SELL paths still use them.
@@ -73,7 +73,8 @@ class DeviceCSR:
         coalesced per-wave x/rhs/y accesses into window-local gathers,
         which costs far more than the ~24% padding it saves.  Off by
         default; kept as an explicit option (and for matrices so ragged
-        that padding dominates)."""
+        that padding dominates).  The sort is applied only above
+        sigma_min_rows rows and when padding exceeds sigma_min_pad x nnz."""
         if self.nslice:
             return self
         import os
@@ -100,7 +101,7 @@ class DeviceCSR:
         total = int(soff[-1].item())
         srows = None
         nnz = self.col.numel()
-        if sigma and total > 1.08 * nnz and n > (1 << 16):
+        if sigma and total > sigma_min_pad * nnz and n > sigma_min_rows:
             # sigma-sorted slices: order rows by length inside sigma-sized
             # windows to cut the slice padding of ragged (coarse SA) levels;
             # the permutation stays window-local, so the scattered x/rhs/y

@@ -11,7 +11,7 @@ import ctypes
 from ._hiplib import lib as _lib
 
 
-class LevelDescC(ctypes.Structure):
+class OpDescC(ctypes.Structure):
     _fields_ = [
         ("nrows", ctypes.c_int64),
         ("nnz", ctypes.c_int64),
@@ -19,35 +19,23 @@ class LevelDescC(ctypes.Structure):
         ("col", ctypes.c_void_p),
         ("val", ctypes.c_void_p),
         ("subw", ctypes.c_int),
-        ("pnnz", ctypes.c_int64),
-        ("pptr", ctypes.c_void_p),
-        ("pcol", ctypes.c_void_p),
-        ("pval", ctypes.c_void_p),
-        ("psubw", ctypes.c_int),
-        ("rnnz", ctypes.c_int64),
-        ("rptr", ctypes.c_void_p),
-        ("rcol", ctypes.c_void_p),
-        ("rval", ctypes.c_void_p),
-        ("rsubw", ctypes.c_int),
-        ("M", ctypes.c_void_p),
-        ("f", ctypes.c_void_p),
-        ("u", ctypes.c_void_p),
-        ("t", ctypes.c_void_p),
         ("nslice", ctypes.c_int64),
         ("soff", ctypes.c_void_p),
         ("scol", ctypes.c_void_p),
         ("sval", ctypes.c_void_p),
-        ("pnslice", ctypes.c_int64),
-        ("psoff", ctypes.c_void_p),
-        ("pscol", ctypes.c_void_p),
-        ("psval", ctypes.c_void_p),
-        ("rnslice", ctypes.c_int64),
-        ("rsoff", ctypes.c_void_p),
-        ("rscol", ctypes.c_void_p),
-        ("rsval", ctypes.c_void_p),
         ("srows", ctypes.c_void_p),
-        ("psrows", ctypes.c_void_p),
-        ("rsrows", ctypes.c_void_p),
+    ]
+
+
+class LevelDescC(ctypes.Structure):
+    _fields_ = [
+        ("A", OpDescC),
+        ("P", OpDescC),
+        ("R", OpDescC),
+        ("M", ctypes.c_void_p),
+        ("f", ctypes.c_void_p),
+        ("u", ctypes.c_void_p),
+        ("t", ctypes.c_void_p),
         ("cheb_degree", ctypes.c_int),
         ("cheb_theta", ctypes.c_double),
         ("cheb_delta", ctypes.c_double),
@@ -61,17 +49,31 @@ class LevelDescC(ctypes.Structure):
         ("ilu_iters", ctypes.c_int),
         ("ilu_damping", ctypes.c_double),
         ("ilu_jdamping", ctypes.c_double),
-        ("lptr", ctypes.c_void_p),
-        ("lcol", ctypes.c_void_p),
-        ("lval", ctypes.c_void_p),
-        ("uptr", ctypes.c_void_p),
-        ("ucol", ctypes.c_void_p),
-        ("uval", ctypes.c_void_p),
+        ("ilu_L", OpDescC),
+        ("ilu_U", OpDescC),
         ("ilu_dinv", ctypes.c_void_p),
         ("ilu_y", ctypes.c_void_p),
         ("ilu_s", ctypes.c_void_p),
         ("ilu_b", ctypes.c_void_p),
     ]
+
+
+def desc_layout():
+    """[(label, value)]: both struct sizes, then every OpDescC and LevelDescC
+    field offset, in the order the library's amg_desc_layout reports them."""
+    out = [("sizeof(OpDesc)", ctypes.sizeof(OpDescC)),
+           ("sizeof(LevelDesc)", ctypes.sizeof(LevelDescC))]
+    for cls in (OpDescC, LevelDescC):
+        out += [(f"offsetof({cls.__name__[:-1]}, {name})", getattr(cls, name).offset)
+                for name, _ in cls._fields_]
+    return out
+
+
+def lib_desc_layout(L):
+    """The same list as the compiled library has it."""
+    buf = (ctypes.c_int64 * 64)()
+    count = L.amg_desc_layout(buf, len(buf))
+    return list(buf[:min(count, len(buf))])
 
 
 _driver_bound = False
@@ -81,21 +83,23 @@ def _bind():
     global _driver_bound
     L = _lib()
     if not _driver_bound:
-        # LevelDescC above is a hand-kept copy of the C struct (amg_common.h):
-        # refuse to pass it on if the two disagree on the size or on where
-        # the last field sits
-        theirs = (L.amg_leveldesc_size(), L.amg_leveldesc_last_offset())
-        ours = (ctypes.sizeof(LevelDescC), LevelDescC.ilu_b.offset)
-        if theirs != ours:
+        # OpDescC / LevelDescC above are hand-kept copies of the C structs
+        # (amg_common.h): refuse to pass them on if the two sides disagree on
+        # a size or on where any field sits
+        ours, theirs = desc_layout(), lib_desc_layout(L)
+        if len(ours) != len(theirs):
             raise RuntimeError(
-                f"LevelDesc layout mismatch: libamghip.so has size {theirs[0]}, "
-                f"ilu_b at {theirs[1]}; LevelDescC has size {ours[0]}, ilu_b at "
-                f"{ours[1]}")
+                f"descriptor layout mismatch: libamghip.so reports {len(theirs)} "
+                f"entries, backend/native.py has {len(ours)}")
+        for (label, mine), lib_value in zip(ours, theirs):
+            if mine != lib_value:
+                raise RuntimeError(
+                    f"descriptor layout mismatch at {label}: libamghip.so has "
+                    f"{lib_value}, backend/native.py has {mine}")
         L.amg_driver_create.argtypes = [
             ctypes.POINTER(LevelDescC), ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-            ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-            ctypes.c_int, ctypes.c_void_p,
+            ctypes.POINTER(OpDescC), ctypes.c_void_p,
         ]
         L.amg_driver_create.restype = ctypes.c_void_p
         L.amg_driver_destroy.argtypes = [ctypes.c_void_p]
@@ -120,6 +124,22 @@ def _bind():
 
 def _ptr(t):
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _op(dst, M, keep, subw=None):
+    """Fill the OpDescC dst from the DeviceCSR M (CSR arrays, plus the SELL
+    image and its sigma permutation when M has them) and append every tensor
+    it now points at to keep.  subw overrides M's own; 0 lets the driver
+    choose."""
+    dst.nrows, dst.nnz = M.nrows, int(M.nnz)
+    dst.ptr, dst.col, dst.val = _ptr(M.ptr), _ptr(M.col), _ptr(M.val)
+    dst.subw = M.subw if subw is None else subw
+    keep.extend([M.ptr, M.col, M.val])
+    if getattr(M, "nslice", 0):
+        dst.nslice = M.nslice
+        dst.soff, dst.scol, dst.sval = _ptr(M.soff), _ptr(M.scol), _ptr(M.sval)
+        dst.srows = _ptr(M.srows)
+        keep.extend([M.soff, M.scol, M.sval, M.srows])
 
 
 class NativeDriver:
@@ -164,62 +184,36 @@ class NativeDriver:
         if amg.coarse_solve is None and not relax_ok(levels[-1].relax):
             raise TypeError("native coarsest smoother unsupported")
 
-        self._keep = []  # tensor refs
+        keep = self._keep = []  # tensor refs
         descs = (LevelDescC * len(levels))()
         n0 = levels[0].A.nrows
         for i, l in enumerate(levels):
             d = descs[i]
             A = l.A
             if isinstance(A, DeviceBSR):
-                d.nrows, d.nnz = A.nrows, int(A.nnz)
+                d.A.nrows, d.A.nnz = A.nrows, int(A.nnz)
                 d.bsize, d.nbrows = A.bsize, A.nbrows
                 d.bptr, d.bcol, d.bval = _ptr(A.ptr), _ptr(A.col), _ptr(A.val)
+                keep.extend([A.ptr, A.col, A.val])
             else:
-                d.nrows, d.nnz = A.nrows, int(A.nnz)
-                d.ptr, d.col, d.val = _ptr(A.ptr), _ptr(A.col), _ptr(A.val)
-                d.subw = A.subw or _auto_subw(A)
+                _op(d.A, A, keep)
             if l.P is not None:
-                P, R = l.P, l.R
-                d.pnnz = int(P.nnz)
-                d.pptr, d.pcol, d.pval = _ptr(P.ptr), _ptr(P.col), _ptr(P.val)
-                d.psubw = P.subw or _auto_subw(P)
-                d.rnnz = int(R.nnz)
-                d.rptr, d.rcol, d.rval = _ptr(R.ptr), _ptr(R.col), _ptr(R.val)
-                d.rsubw = R.subw or _auto_subw(R)
-            if getattr(A, "nslice", 0):
-                d.nslice = A.nslice
-                d.soff, d.scol, d.sval = _ptr(A.soff), _ptr(A.scol), _ptr(A.sval)
-                d.srows = _ptr(A.srows)
-                self._keep.extend([A.soff, A.scol, A.sval, A.srows])
-            if l.P is not None and getattr(l.P, "nslice", 0):
-                d.pnslice = l.P.nslice
-                d.psoff, d.pscol, d.psval = (_ptr(l.P.soff), _ptr(l.P.scol),
-                                             _ptr(l.P.sval))
-                d.psrows = _ptr(l.P.srows)
-                self._keep.extend([l.P.soff, l.P.scol, l.P.sval, l.P.srows])
-            if l.R is not None and getattr(l.R, "nslice", 0):
-                d.rnslice = l.R.nslice
-                d.rsoff, d.rscol, d.rsval = (_ptr(l.R.soff), _ptr(l.R.scol),
-                                             _ptr(l.R.sval))
-                d.rsrows = _ptr(l.R.srows)
-                self._keep.extend([l.R.soff, l.R.scol, l.R.sval, l.R.srows])
+                _op(d.P, l.P, keep)
+                _op(d.R, l.R, keep)
             relax = l.relax
             if isinstance(relax, ILU0):
                 d.ilu_iters = relax.solve_iters
                 d.ilu_damping = relax.damping
                 d.ilu_jdamping = relax.solve_damping
-                d.lptr, d.lcol, d.lval = (_ptr(relax.L.ptr), _ptr(relax.L.col),
-                                          _ptr(relax.L.val))
-                d.uptr, d.ucol, d.uval = (_ptr(relax.U.ptr), _ptr(relax.U.col),
-                                          _ptr(relax.U.val))
+                # subw 2: the width the triangular sweeps have always run with
+                _op(d.ilu_L, relax.L, keep, subw=2)
+                _op(d.ilu_U, relax.U, keep, subw=2)
                 d.ilu_dinv = _ptr(relax.Dinv)
                 work = [torch.empty(A.nrows, dtype=torch.float64,
                                     device=backend.device) for _ in range(3)]
                 d.ilu_y, d.ilu_s, d.ilu_b = (_ptr(work[0]), _ptr(work[1]),
                                              _ptr(work[2]))
-                self._keep.extend([relax.L.ptr, relax.L.col, relax.L.val,
-                                   relax.U.ptr, relax.U.col, relax.U.val,
-                                   relax.Dinv] + work)
+                keep.extend([relax.Dinv] + work)
             elif isinstance(relax, Chebyshev):
                 d.cheb_degree = relax.degree
                 d.cheb_theta = relax.theta
@@ -228,42 +222,35 @@ class NativeDriver:
                 cheb_d = torch.empty(A.nrows, dtype=torch.float64,
                                      device=backend.device)
                 d.cheb_d = _ptr(cheb_d)
-                self._keep.append(cheb_d)
+                keep.append(cheb_d)
                 d.M = _ptr(relax.Dinv)  # optional D^-1 scaling (may be null)
                 if relax.Dinv is not None:
-                    self._keep.append(relax.Dinv)
-            else:
-                d.M = _ptr(relax.M if relax is not None else None)
+                    keep.append(relax.Dinv)
+            elif relax is not None:
+                d.M = _ptr(relax.M)
+                keep.append(relax.M)
             d.f = _ptr(l.f)
             d.u = _ptr(l.u)
             d.t = _ptr(l.t)
-            self._keep.extend([A.ptr, A.col, A.val, l.f, l.u, l.t])
-            if l.P is not None:
-                self._keep.extend([l.P.ptr, l.P.col, l.P.val, l.R.ptr, l.R.col, l.R.val])
-            if relax is not None and not isinstance(relax, (Chebyshev, ILU0)):
-                self._keep.append(relax.M)
+            keep.extend([l.f, l.u, l.t])
 
         inv = amg.coarse_solve.inv if amg.coarse_solve is not None else None
         if inv is not None:
-            self._keep.append(inv)
+            keep.append(inv)
         prm = amg.prm
         L = _bind()
         stream = torch.cuda.current_stream().cuda_stream
+        a64 = None
         if self._mixed:
             # the Krylov loop keeps iterating with the fp64 fine operator;
             # the LevelDescs above point at the fp32 hierarchy for the cycle
-            A64 = amg._A64
-            self._keep.extend([A64.ptr, A64.col, A64.val])
-            a64 = (int(A64.nnz), _ptr(A64.ptr), _ptr(A64.col), _ptr(A64.val),
-                   A64.subw or _auto_subw(A64))
-        else:
-            a64 = (0, None, None, None, 0)
+            a64 = OpDescC()
+            _op(a64, amg._A64, keep)
         self.handle = L.amg_driver_create(
             descs, len(levels), _ptr(inv),
             amg.coarse_solve.n if amg.coarse_solve is not None else 0,
             int(prm["npre"]), int(prm["npost"]), int(prm["ncycle"]),
-            int(prm["pre_cycles"]), int(self._mixed), a64[0], a64[1], a64[2],
-            a64[3], a64[4], ctypes.c_void_p(stream),
+            int(prm["pre_cycles"]), int(self._mixed), a64, ctypes.c_void_p(stream),
         )
         if not self.handle:
             raise RuntimeError("amg_driver_create failed")
@@ -301,14 +288,6 @@ class NativeDriver:
             _bind().amg_driver_destroy(self.handle)
         except Exception:
             pass
-
-
-def _auto_subw(A):
-    m = A.nnz / max(A.nrows, 1)
-    for lim, sw in ((4, 2), (10, 4), (24, 8), (128, 16)):
-        if m <= lim:
-            return sw
-    return 32
 
 
 def try_native(make_solver_obj):

@@ -47,47 +47,44 @@ static inline int amg_nblocks(int64_t work, int block = 256, int cap = 2048) {
     return (int)b;
 }
 
-// Per-level operator descriptor consumed by the native solve driver
-// (driver.hip amg_driver_create); filled either from Python (backend/
-// native.py, torch tensors) or from the torch-free GPU C API
-// (capi_gpu.hip, raw hipMalloc buffers).
-struct LevelDesc {
+// Sub-wave width of the CSR row kernels by mean row length (lanes per row).
+static inline int amg_pick_subw(int64_t nrows, int64_t nnz) {
+    double m = nrows ? (double)nnz / (double)nrows : 1.0;
+    if (m <= 4) return 2;
+    if (m <= 10) return 4;
+    if (m <= 24) return 8;
+    if (m <= 128) return 16;
+    return 32;
+}
+
+// One sparse operator as the native solve driver (driver.hip) sees it: CSR
+// plus an optional SELL-64 image (see kernels.hip).  val/sval hold double, or
+// float in the fp32 hierarchy of a mixed-precision solve.
+struct OpDesc {
     int64_t nrows, nnz;
     const int *ptr;
     const int *col;
-    const double *val;
-    int subw;
-    int64_t pnnz;  // P: nrows x next->nrows
-    const int *pptr;
-    const int *pcol;
-    const double *pval;
-    int psubw;
-    int64_t rnnz;  // R: next->nrows x nrows
-    const int *rptr;
-    const int *rcol;
-    const double *rval;
-    int rsubw;
+    const void *val;
+    int subw;        // CSR lanes per row; <= 0: chosen at driver create
+    int64_t nslice;  // 0 = no SELL image
+    const int64_t *soff;
+    const int *scol;
+    const void *sval;
+    const int *srows;  // optional sigma-sort permutation (slot -> row, < 0 = pad)
+};
+
+// Per-level descriptor consumed by amg_driver_create; filled either from
+// Python (backend/native.py, torch tensors) or from the torch-free GPU C API
+// (capi_gpu.hip, raw device buffers).  backend/native.py keeps a ctypes twin
+// and checks it against amg_desc_layout (driver.hip) when it binds.
+struct LevelDesc {
+    OpDesc A;  // A.nrows is the level size (CSR arrays unused when bsize > 0)
+    OpDesc P;  // nrows x next->nrows
+    OpDesc R;  // next->nrows x nrows
     const double *M;  // diagonal smoother weights
     double *f;
     double *u;
     double *t;  // workspace (f/u unused at level 0)
-    // optional SELL-64 images of A / P / R (see kernels.hip)
-    int64_t nslice;  // 0 = no SELL
-    const int64_t *soff;
-    const int *scol;
-    const void *sval;
-    int64_t pnslice;
-    const int64_t *psoff;
-    const int *pscol;
-    const void *psval;
-    int64_t rnslice;
-    const int64_t *rsoff;
-    const int *rscol;
-    const void *rsval;
-    // optional sigma-sort permutations (slot -> row id, < 0 = padding)
-    const int *srows;
-    const int *psrows;
-    const int *rsrows;
     // Chebyshev smoothing (cheb_degree > 0 replaces the diagonal smoother;
     // M then holds the optional D^-1 scaling or null)
     int cheb_degree;
@@ -95,7 +92,7 @@ struct LevelDesc {
     double cheb_delta;
     double cheb_sigma1;
     void *cheb_d;  // extra per-level work vector for the recurrence
-    // BSR storage of A (bsize > 0; ptr/col/val above are then unused for A)
+    // BSR storage of A (bsize > 0)
     int bsize;
     int64_t nbrows;
     const int *bptr;
@@ -103,19 +100,15 @@ struct LevelDesc {
     const double *bval;
     // ILU(0) smoothing via damped-Jacobi iterated triangular solves
     // (ilu_iters > 0; the reference's GPU-native ilu_solve.hpp route).
-    // L strictly lower (unit diag implied), U strictly upper; ilu_dinv is
-    // the inverted diagonal of U.
+    // ilu_L strictly lower (unit diag implied), ilu_U strictly upper;
+    // ilu_dinv is the inverted diagonal of U.
     int ilu_iters;
-    double ilu_damping;       // outer relaxation damping
-    double ilu_jdamping;      // inner Jacobi damping (0.72)
-    const int *lptr;
-    const int *lcol;
-    const double *lval;
-    const int *uptr;
-    const int *ucol;
-    const double *uval;
+    double ilu_damping;   // outer relaxation damping
+    double ilu_jdamping;  // inner Jacobi damping (0.72)
+    OpDesc ilu_L;
+    OpDesc ilu_U;
     const double *ilu_dinv;
-    double *ilu_y;            // work vectors (level-sized)
+    double *ilu_y;  // work vectors (level-sized)
     double *ilu_s;
     double *ilu_b;
 };

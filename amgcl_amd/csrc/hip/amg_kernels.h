@@ -7,7 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-struct LevelDesc;  // amg_common.h
+struct OpDesc;  // amg_common.h
+struct LevelDesc;
 
 extern "C" {
 
@@ -116,8 +117,7 @@ int amg_spgemm_fill(int64_t an, const int *aptr, const int *acol, const double *
 // ---- driver.hip: native solve driver entry points
 void *amg_driver_create(const LevelDesc *levels, int nlevels, const void *coarse_inv,
                         int64_t ncoarse, int npre, int npost, int ncycle, int pre_cycles,
-                        int f32, int64_t a64_nnz, const int *a64_ptr, const int *a64_col,
-                        const double *a64_val, int a64_subw, hipStream_t stream);
+                        int f32, const OpDesc *a64, hipStream_t stream);
 void amg_driver_destroy(void *h);
 int amg_driver_precond(void *h, const double *rhs, double *x, double *x_swap);
 int amg_driver_cg(void *h, const double *rhs, double *x, double *r, double *s, double *p,

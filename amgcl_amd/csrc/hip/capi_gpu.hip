@@ -85,13 +85,14 @@ double *dalloc(size_t n) {
     return d;
 }
 
-static int pick_subw(int64_t nrows, int64_t nnz) {
-    double m = nrows ? (double)nnz / (double)nrows : 1.0;
-    if (m <= 4) return 2;
-    if (m <= 10) return 4;
-    if (m <= 24) return 8;
-    if (m <= 128) return 16;
-    return 32;
+// CSR part of an operator descriptor; subw stays 0 (chosen at driver create)
+void fill_op(OpDesc &op, int64_t n, int64_t nnz, const int *ptr, const int *col,
+             const double *val) {
+    op.nrows = n;
+    op.nnz = nnz;
+    op.ptr = ptr;
+    op.col = col;
+    op.val = val;
 }
 
 struct GpuSolver {
@@ -112,13 +113,9 @@ struct GpuSolver {
         if (!pool_blobs.empty()) (void)hipStreamSynchronize(0);
     }
 
-    void *keep(void *p) {
+    template <typename T>
+    T *keep(T *p) {
         if (p) blobs.push_back(p);
-        return p;
-    }
-
-    void *keep_pool(void *p) {
-        if (p) pool_blobs.push_back(p);
         return p;
     }
 };
@@ -172,12 +169,11 @@ __global__ void capi_slicew_k(int64_t n, int64_t nslice, const int *__restrict__
     }
 }
 
-namespace {
-
 struct DevSetupFail {};  // -> host fallback
 
-// tracked hipMalloc: `keep` buffers live with the solver, `tmp` buffers are
-// freed when the Tracker goes out of scope (per-level scratch)
+// Tracked stream-ordered allocations, freed when the Tracker goes out of
+// scope: per-level scratch, and the hierarchy's own buffers (`own` in
+// build_device_levels) until a finished setup hands them to the solver
 struct Tracker {
     std::vector<void *> bufs;
     ~Tracker() {
@@ -197,21 +193,13 @@ struct Tracker {
         bufs.push_back(p);
         return (T *)p;
     }
-    void *release(void *p) {  // transfer ownership to the caller
-        for (size_t i = 0; i < bufs.size(); ++i)
-            if (bufs[i] == p) {
-                bufs.erase(bufs.begin() + i);
-                return p;
-            }
-        return p;
-    }
 };
 
-static void dev_check(int rc) {
+void dev_check(int rc) {
     if (rc != 0) throw DevSetupFail{};
 }
 
-static void trace(const char *what, long long a = -1, long long b = -1) {
+void trace(const char *what, long long a = -1, long long b = -1) {
     if (!getenv("AMGCL_CAPI_TRACE")) return;
     fprintf(stderr, "[capi setup] %s %lld %lld\n", what, a, b);
     (void)hipDeviceSynchronize();
@@ -225,7 +213,7 @@ struct DevCsr {
     double *val = nullptr;
 };
 
-static int read_i32(const int *dev_p) {
+int read_i32(const int *dev_p) {
     int v = 0;
     if (hipMemcpy(&v, dev_p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
         throw DevSetupFail{};
@@ -233,20 +221,18 @@ static int read_i32(const int *dev_p) {
 }
 
 // scan counts stored at p[1..n] in place, p[0] = 0; returns total
-static int scan_counts(int *p, int64_t n) {
+int scan_counts(int *p, int64_t n) {
     dev_check(amg_scan_i32(p + 1, n, 0));
     return read_i32(p + n);
 }
 
-// SELL-64 image built on the device (same layout as DeviceCSR.build_sell)
-static void build_sell_capi(GpuSolver *S, int64_t n, const int *ptr, const int *col,
-                            const double *val, int64_t &nslice_out,
-                            const int64_t *&soff_out, const int *&scol_out,
-                            const void *&sval_out) {
-    int64_t nslice = (n + 63) / 64;
+// SELL-64 image of op's CSR arrays, built on the device into buffers of `own`
+// (same layout as DeviceCSR.build_sell)
+void build_sell_capi(Tracker &own, OpDesc &op) {
+    const int64_t n = op.nrows, nslice = (n + 63) / 64;
     Tracker tmp;
     int *w = tmp.alloc<int>(nslice);
-    capi_slicew_k<<<amg_nblocks(nslice), 256, 0, 0>>>(n, nslice, ptr, w);
+    capi_slicew_k<<<amg_nblocks(nslice), 256, 0, 0>>>(n, nslice, op.ptr, w);
     dev_check((int)hipGetLastError());
     std::vector<int> wh(nslice);
     if (hipMemcpy(wh.data(), w, nslice * sizeof(int), hipMemcpyDeviceToHost) !=
@@ -255,24 +241,22 @@ static void build_sell_capi(GpuSolver *S, int64_t n, const int *ptr, const int *
     std::vector<int64_t> soff(nslice + 1, 0);
     for (int64_t s = 0; s < nslice; ++s) soff[s + 1] = soff[s] + (int64_t)wh[s] * 64;
     int64_t total = soff[nslice];
-    int64_t *soff_d = (int64_t *)S->keep(upload(soff));
-    if (!soff_d) throw DevSetupFail{};
-    Tracker out;
-    int *scol = out.alloc<int>(total);
-    double *sval = out.alloc<double>(total);
-    dev_check(amg_sell_fill_f64(n, nslice, ptr, col, val, soff_d, nullptr, scol,
-                                sval, 0));
-    S->keep_pool(out.release(scol));
-    S->keep_pool(out.release(sval));
-    nslice_out = nslice;
-    soff_out = soff_d;
-    scol_out = scol;
-    sval_out = sval;
+    int64_t *soff_d = own.alloc<int64_t>(nslice + 1);
+    if (!upload_bytes(soff_d, soff.data(), (nslice + 1) * sizeof(int64_t)))
+        throw DevSetupFail{};
+    int *scol = own.alloc<int>(total);
+    double *sval = own.alloc<double>(total);
+    dev_check(amg_sell_fill_f64(n, nslice, op.ptr, op.col, (const double *)op.val,
+                                soff_d, nullptr, scol, sval, 0));
+    op.nslice = nslice;
+    op.soff = soff_d;
+    op.scol = scol;
+    op.sval = sval;
 }
 
 // One SpGEMM product C = A*B on the device (ownership of C's arrays moves to
 // the caller's tracker)
-static DevCsr spgemm_dev(Tracker &own, const DevCsr &A, const DevCsr &B, int sort) {
+DevCsr spgemm_dev(Tracker &own, const DevCsr &A, const DevCsr &B, int sort) {
     Tracker tmp;
     int *ub = tmp.alloc<int>(A.n);
     int *cptr = own.alloc<int>(A.n + 1, true);
@@ -296,7 +280,7 @@ static DevCsr spgemm_dev(Tracker &own, const DevCsr &A, const DevCsr &B, int sor
 
 // Build the device part of the hierarchy; returns the handoff matrix
 // downloaded to the host (tail continues in the host engine).
-static Csr build_device_levels(GpuSolver *S, int n, const int *ptr, const int *col,
+Csr build_device_levels(GpuSolver *S, int n, const int *ptr, const int *col,
                                const double *val, const Params &p,
                                std::vector<LevelDesc> &descs, double &eps_inout) {
     const int handoff = p.geti("precond.device_handoff", 20000);
@@ -304,7 +288,7 @@ static Csr build_device_levels(GpuSolver *S, int n, const int *ptr, const int *c
     const int max_levels = p.geti("precond.max_levels", 20);
     const std::string relax = p.gets("precond.relax.type", "spai0");
     const double damping = p.getf("precond.relax.damping", 0.72);
-    const int64_t sell_min = 500000;
+    const int64_t sell_min = p.geti("precond.sell_min_rows", 500000);
     if (relax != "spai0" && relax != "damped_jacobi") throw DevSetupFail{};
 
     Tracker own;  // per-hierarchy ownership; transferred to S->keep on success
@@ -400,42 +384,22 @@ static Csr build_device_levels(GpuSolver *S, int n, const int *ptr, const int *c
         // record this level
         LevelDesc dsc;
         std::memset(&dsc, 0, sizeof dsc);
-        dsc.nrows = A.n;
-        dsc.nnz = A.nnz;
-        dsc.ptr = A.ptr;
-        dsc.col = A.col;
-        dsc.val = A.val;
-        dsc.subw = pick_subw(A.n, A.nnz);
-        dsc.pnnz = P.nnz;
-        dsc.pptr = P.ptr;
-        dsc.pcol = P.col;
-        dsc.pval = P.val;
-        dsc.psubw = pick_subw(P.n, P.nnz);
-        dsc.rnnz = R.nnz;
-        dsc.rptr = R.ptr;
-        dsc.rcol = R.col;
-        dsc.rval = R.val;
-        dsc.rsubw = pick_subw(R.n, R.nnz);
+        fill_op(dsc.A, A.n, A.nnz, A.ptr, A.col, A.val);
+        fill_op(dsc.P, P.n, P.nnz, P.ptr, P.col, P.val);
+        fill_op(dsc.R, R.n, R.nnz, R.ptr, R.col, R.val);
         dsc.M = M;
-        dsc.f = (double *)own.alloc<double>(A.n, true);
-        dsc.u = (double *)own.alloc<double>(A.n, true);
-        dsc.t = (double *)own.alloc<double>(A.n, true);
+        dsc.f = own.alloc<double>(A.n, true);
+        dsc.u = own.alloc<double>(A.n, true);
+        dsc.t = own.alloc<double>(A.n, true);
         trace("record");
-        if (getenv("AMGCL_CAPI_NO_SELL")) {
-            descs.push_back(dsc);
-            A = Ac;
-            continue;
+        if (!getenv("AMGCL_CAPI_NO_SELL")) {
+            if (A.n >= sell_min) build_sell_capi(own, dsc.A);
+            if (P.n >= sell_min) {
+                build_sell_capi(own, dsc.P);
+                build_sell_capi(own, dsc.R);
+            }
+            trace("sell", dsc.A.nslice, dsc.P.nslice);
         }
-        if (A.n >= sell_min)
-            build_sell_capi(S, A.n, A.ptr, A.col, A.val, dsc.nslice, dsc.soff,
-                            dsc.scol, dsc.sval);
-        if (P.n >= sell_min) {
-            build_sell_capi(S, P.n, P.ptr, P.col, P.val, dsc.pnslice, dsc.psoff,
-                            dsc.pscol, dsc.psval);
-            build_sell_capi(S, R.n, R.ptr, R.col, R.val, dsc.rnslice, dsc.rsoff,
-                            dsc.rscol, dsc.rsval);
-        }
-        trace("sell");
         descs.push_back(dsc);
         A = Ac;
     }
@@ -457,13 +421,10 @@ static Csr build_device_levels(GpuSolver *S, int n, const int *ptr, const int *c
     tail.val = std::move(hv);
     // success: everything still owned by `own` now belongs to the solver
     // (hipMallocAsync memory -> freed with hipFreeAsync at destroy)
-    for (void *b : own.bufs) S->keep_pool(b);
-    own.bufs.clear();
+    S->pool_blobs.swap(own.bufs);
     eps_inout = eps;
     return tail;
 }
-
-}  // namespace (inner)
 
 }  // namespace
 
@@ -494,7 +455,7 @@ extern "C" void *amgcl_amd_gpu_solver_create(int n, const int *ptr, const int *c
             tail = build_device_levels(S, n, ptr, col, val, p, descs, eps);
             have_tail = true;
         } catch (DevSetupFail &) {
-            descs.clear();  // partial buffers stay in S->blobs until destroy
+            descs.clear();  // the failed setup has freed everything it made
         }
     }
 
@@ -522,34 +483,23 @@ extern "C" void *amgcl_amd_gpu_solver_create(int n, const int *ptr, const int *c
         auto &L = P.lvl[i];
         LevelDesc &d = descs[base0 + i];
         std::memset(&d, 0, sizeof d);
-        d.nrows = L.A.n;
-        d.nnz = L.A.nnz();
-        d.ptr = (const int *)S->keep(upload(L.A.ptr));
-        d.col = (const int *)S->keep(upload(L.A.col));
-        d.val = (const double *)S->keep(upload(L.A.val));
-        d.subw = pick_subw(d.nrows, d.nnz);
-        if (L.P.n) {
-            d.pnnz = L.P.nnz();
-            d.pptr = (const int *)S->keep(upload(L.P.ptr));
-            d.pcol = (const int *)S->keep(upload(L.P.col));
-            d.pval = (const double *)S->keep(upload(L.P.val));
-            d.psubw = pick_subw(L.P.n, d.pnnz);
-            d.rnnz = L.R.nnz();
-            d.rptr = (const int *)S->keep(upload(L.R.ptr));
-            d.rcol = (const int *)S->keep(upload(L.R.col));
-            d.rval = (const double *)S->keep(upload(L.R.val));
-            d.rsubw = pick_subw(L.R.n, d.rnnz);
-        }
-        if (!L.M.empty()) d.M = (const double *)S->keep(upload(L.M));
-        d.f = (double *)S->keep(dalloc(L.A.n));
-        d.u = (double *)S->keep(dalloc(L.A.n));
-        d.t = (double *)S->keep(dalloc(L.A.n));
-        // hipMalloc failure shows up as a null field: fail the create
+        // hipMalloc failure shows up as a null array: fail the create
         // cleanly instead of handing the driver dangling level pointers
-        oom |= !d.ptr || !d.col || !d.val || !d.f || !d.u || !d.t;
-        oom |= (L.P.n != 0) && (!d.pptr || !d.pcol || !d.pval ||
-                                !d.rptr || !d.rcol || !d.rval);
-        oom |= !L.M.empty() && !d.M;
+        auto upload_op = [&](OpDesc &op, const Csr &M) {
+            fill_op(op, M.n, M.nnz(), S->keep(upload(M.ptr)), S->keep(upload(M.col)),
+                    S->keep(upload(M.val)));
+            oom |= !op.ptr || !op.col || !op.val;
+        };
+        upload_op(d.A, L.A);
+        if (L.P.n) {
+            upload_op(d.P, L.P);
+            upload_op(d.R, L.R);
+        }
+        if (!L.M.empty()) d.M = S->keep(upload(L.M));
+        d.f = S->keep(dalloc(L.A.n));
+        d.u = S->keep(dalloc(L.A.n));
+        d.t = S->keep(dalloc(L.A.n));
+        oom |= !d.f || !d.u || !d.t || (!L.M.empty() && !d.M);
     }
     if (oom) {
         delete S;
@@ -576,20 +526,20 @@ extern "C" void *amgcl_amd_gpu_solver_create(int n, const int *ptr, const int *c
                 for (int r = 0; r < m; ++r) inv[(size_t)r * m + c] = x1[r];
             }
         }
-        inv_d = (const double *)S->keep(upload(inv));
+        inv_d = S->keep(upload(inv));
     }
 
     S->driver = amg_driver_create(descs.data(), (int)descs.size(), inv_d, ncoarse,
-                                  P.npre, P.npost, P.ncycle, 1, 0, 0, nullptr,
-                                  nullptr, nullptr, 0, (hipStream_t)0);
+                                  P.npre, P.npost, P.ncycle, 1, 0, nullptr,
+                                  (hipStream_t)0);
     if (!S->driver) {
         delete S;
         return nullptr;
     }
     int nwork = S->type == "cg" ? 5 : 8;
-    for (int i = 0; i < nwork; ++i) S->work.push_back((double *)S->keep(dalloc(n)));
-    S->rhs_d = (double *)S->keep(dalloc(n));
-    S->x_d = (double *)S->keep(dalloc(n));
+    for (int i = 0; i < nwork; ++i) S->work.push_back(S->keep(dalloc(n)));
+    S->rhs_d = S->keep(dalloc(n));
+    S->x_d = S->keep(dalloc(n));
     // setup kernels (SELL fills etc.) may still be in flight; finish them so
     // create/solve wall times split honestly for callers that time them
     (void)hipDeviceSynchronize();

@@ -81,10 +81,6 @@ __global__ void relax_zero_k(int64_t n, const T *__restrict__ M,
     for (; i < n; i += stride) xn[i] = M[i] * rhs[i];
 }
 
-static inline int nblocks_d(int64_t work, int block = 256, int cap = 2048) {
-    return amg_nblocks(work, block, cap);
-}
-
 struct GraphEntry {
     const double *rhs;
     double *x;
@@ -116,11 +112,7 @@ struct Driver {
     // mixed precision: the cycle runs fp32 on the (fp32) LevelDescs while the
     // Krylov loop keeps the fp64 fine operator below + f32 cast buffers
     int f32;
-    int64_t a64_nnz;
-    const int *a64_ptr;
-    const int *a64_col;
-    const double *a64_val;
-    int a64_subw;
+    OpDesc a64;
     float *cb_r, *cb_x, *cb_s;  // level-0-sized cast buffers (f32 mode)
 };
 
@@ -130,37 +122,37 @@ struct Driver {
         if (_rc) return _rc;            \
     } while (0)
 
-// residual through whichever storage this level's A carries (BSR > SELL > CSR)
+// y = alpha op x + beta y and r = rhs - op x, through the operator's SELL
+// image when it has one, else CSR: the only place that choice is made
+template <typename T>
+static int op_spmv(Driver *D, const OpDesc &op, const T *x, double alpha, double beta,
+                   T *y) {
+    if (op.nslice)
+        return sell_spmv<T>(op.nrows, op.nslice, op.soff, op.scol, (const T *)op.sval,
+                            op.srows, x, alpha, beta, y, D->stream);
+    return spmv<T>(op.nrows, op.nnz, op.ptr, op.col, (const T *)op.val, x, alpha, beta, y,
+                   op.subw, D->stream);
+}
+
+template <typename T>
+static int op_residual(Driver *D, const OpDesc &op, const T *rhs, const T *x, T *r) {
+    if (op.nslice)
+        return sell_residual<T>(op.nrows, op.nslice, op.soff, op.scol,
+                                (const T *)op.sval, op.srows, rhs, x, r, D->stream);
+    return residual<T>(op.nrows, op.nnz, op.ptr, op.col, (const T *)op.val, rhs, x, r,
+                       op.subw, D->stream);
+}
+
+// residual through whichever storage this level's A carries (BSR, else L.A)
 template <typename T>
 static int level_residual(Driver *D, const LevelDesc &L, const T *rhs, const T *x,
                           T *r) {
-    if (L.bsize) {
-        if constexpr (std::is_same_v<T, double>)
-            return amg_bsr_residual_f64(L.nbrows, L.bsize, L.bptr, L.bcol, L.bval, rhs,
-                                        x, r, D->stream);
-        else
-            return (int)hipErrorInvalidValue;
-    }
-    if (L.nslice)
-        return sell_residual<T>(L.nrows, L.nslice, L.soff, L.scol, (const T *)L.sval,
-                                L.srows, rhs, x, r, D->stream);
-    return residual<T>(L.nrows, L.nnz, L.ptr, L.col, (const T *)L.val, rhs, x, r, L.subw,
-                       D->stream);
-}
-
-// y = P x + beta y (prolong) or y = R x + beta y, through the operator's SELL
-// image when it has one, else CSR; nrows is the row count of that operator
-template <typename T>
-static int transfer(Driver *D, const LevelDesc &L, bool prolong, int64_t nrows,
-                    const T *x, double beta, T *y) {
-    const bool p = prolong;
-    if (const int64_t nslice = p ? L.pnslice : L.rnslice)
-        return sell_spmv<T>(nrows, nslice, p ? L.psoff : L.rsoff, p ? L.pscol : L.rscol,
-                            (const T *)(p ? L.psval : L.rsval), p ? L.psrows : L.rsrows,
-                            x, 1.0, beta, y, D->stream);
-    return spmv<T>(nrows, p ? L.pnnz : L.rnnz, p ? L.pptr : L.rptr, p ? L.pcol : L.rcol,
-                   (const T *)(p ? L.pval : L.rval), x, 1.0, beta, y,
-                   p ? L.psubw : L.rsubw, D->stream);
+    if (!L.bsize) return op_residual<T>(D, L.A, rhs, x, r);
+    if constexpr (std::is_same_v<T, double>)
+        return amg_bsr_residual_f64(L.nbrows, L.bsize, L.bptr, L.bcol, L.bval, rhs, x, r,
+                                    D->stream);
+    else
+        return (int)hipErrorInvalidValue;
 }
 
 // Chebyshev polynomial smoothing, in place on x (driver twin of
@@ -170,15 +162,15 @@ template <typename T>
 static int cheb_apply(Driver *D, const LevelDesc &L, const T *rhs, T *x, T *r) {
     T *d = (T *)L.cheb_d;
     CHK(level_residual<T>(D, L, rhs, x, r));
-    if (L.M) CHK(vmul<T>(L.nrows, 1.0, (const T *)L.M, r, 0.0, r, D->stream));
+    if (L.M) CHK(vmul<T>(L.A.nrows, 1.0, (const T *)L.M, r, 0.0, r, D->stream));
     double rho = 1.0 / L.cheb_sigma1;
-    CHK(axpby<T>(L.nrows, 1.0 / L.cheb_theta, r, 0.0, d, D->stream));
+    CHK(axpby<T>(L.A.nrows, 1.0 / L.cheb_theta, r, 0.0, d, D->stream));
     for (int k = 0; k < L.cheb_degree; ++k) {
-        CHK(axpby<T>(L.nrows, 1.0, d, 1.0, x, D->stream));
+        CHK(axpby<T>(L.A.nrows, 1.0, d, 1.0, x, D->stream));
         CHK(level_residual<T>(D, L, rhs, x, r));
-        if (L.M) CHK(vmul<T>(L.nrows, 1.0, (const T *)L.M, r, 0.0, r, D->stream));
+        if (L.M) CHK(vmul<T>(L.A.nrows, 1.0, (const T *)L.M, r, 0.0, r, D->stream));
         double rho_next = 1.0 / (2.0 * L.cheb_sigma1 - rho);
-        CHK(axpby<T>(L.nrows, 2.0 * rho_next / L.cheb_delta, r, rho_next * rho, d,
+        CHK(axpby<T>(L.A.nrows, 2.0 * rho_next / L.cheb_delta, r, rho_next * rho, d,
                      D->stream));
         rho = rho_next;
     }
@@ -197,7 +189,7 @@ static int ilu_apply(Driver *D, const LevelDesc &L, const T *rhs, T *x, T *t) {
 template <>
 int ilu_apply<double>(Driver *D, const LevelDesc &L, const double *rhs, double *x,
                       double *t) {
-    const int64_t n = L.nrows;
+    const int64_t n = L.A.nrows;
     hipStream_t st = D->stream;
     double *y = L.ilu_y, *s = L.ilu_s, *b = L.ilu_b;
     const double om = L.ilu_jdamping;
@@ -205,7 +197,7 @@ int ilu_apply<double>(Driver *D, const LevelDesc &L, const double *rhs, double *
     // lower: (I + L) y = t
     CHK(hipMemcpyAsync(y, t, n * sizeof(double), hipMemcpyDeviceToDevice, st));
     for (int it = 0; it < L.ilu_iters; ++it) {
-        CHK(amg_spmv_f64(n, 0, L.lptr, L.lcol, L.lval, y, -1.0, 0.0, s, 2, st));
+        CHK(op_spmv<double>(D, L.ilu_L, y, -1.0, 0.0, s));
         CHK(amg_axpby_f64(n, 1.0, t, 1.0, s, st));
         CHK(amg_axpby_f64(n, om, s, 1.0 - om, y, st));
     }
@@ -213,7 +205,7 @@ int ilu_apply<double>(Driver *D, const LevelDesc &L, const double *rhs, double *
     CHK(hipMemcpyAsync(b, y, n * sizeof(double), hipMemcpyDeviceToDevice, st));
     CHK(amg_vmul_f64(n, 1.0, L.ilu_dinv, b, 0.0, y, st));
     for (int it = 0; it < L.ilu_iters; ++it) {
-        CHK(amg_spmv_f64(n, 0, L.uptr, L.ucol, L.uval, y, -1.0, 0.0, s, 2, st));
+        CHK(op_spmv<double>(D, L.ilu_U, y, -1.0, 0.0, s));
         CHK(amg_axpby_f64(n, 1.0, b, 1.0, s, st));
         CHK(amg_vmul_f64(n, 1.0, L.ilu_dinv, s, 0.0, s, st));
         CHK(amg_axpby_f64(n, om, s, 1.0 - om, y, st));
@@ -239,26 +231,26 @@ static int relax_swap(Driver *D, const LevelDesc &L, const T *rhs, T **x, T **xn
                                   *x, *xn, D->stream));
         else
             return (int)hipErrorInvalidValue;
-        CHK(axpby<T>(L.nrows, 1.0, *x, 1.0, *xn, D->stream));
+        CHK(axpby<T>(L.A.nrows, 1.0, *x, 1.0, *xn, D->stream));
         std::swap(*x, *xn);
         return 0;
     }
-    if (L.nslice) {
-        CHK(sell_relax<T>(L.nrows, L.nslice, L.soff, L.scol, (const T *)L.sval, L.srows,
-                          (const T *)L.M, rhs, *x, *xn, D->stream));
-        std::swap(*x, *xn);
-        return 0;
-    }
-    int subw = L.subw;
-    int grid = nblocks_d(L.nrows * subw);
-    const T *val = (const T *)L.val;
+    const OpDesc &A = L.A;
     const T *M = (const T *)L.M;
+    if (A.nslice) {
+        CHK(sell_relax<T>(A.nrows, A.nslice, A.soff, A.scol, (const T *)A.sval, A.srows,
+                          M, rhs, *x, *xn, D->stream));
+        std::swap(*x, *xn);
+        return 0;
+    }
+    int grid = amg_nblocks(A.nrows * A.subw);
+    const T *val = (const T *)A.val;
 #define RCASE(SW)                                                                       \
     case SW:                                                                            \
-        relax_swap_k<SW, T><<<grid, 256, 0, D->stream>>>(L.nrows, L.ptr, L.col, val,    \
-                                                         M, rhs, *x, *xn);              \
+        relax_swap_k<SW, T><<<grid, 256, 0, D->stream>>>(A.nrows, A.ptr, A.col, val, M, \
+                                                         rhs, *x, *xn);                 \
         break;
-    switch (subw) {
+    switch (A.subw) {
         RCASE(1) RCASE(2) RCASE(4) RCASE(8) RCASE(16) RCASE(32) RCASE(64)
         default: return hipErrorInvalidValue;
     }
@@ -279,18 +271,18 @@ static int cycle(Driver *D, int li, const T *f, T **u_io, T **scratch, bool u_is
     auto relax_zero = [&](LevelDesc &LL, const T *ff, T **u2, T **sc) -> int {
         if (LL.cheb_degree || LL.bsize || LL.ilu_iters) {
             // no fused zero-guess form for these smoothers: clear + general
-            CHK(fill<T>(LL.nrows, 0.0, *u2, D->stream));
+            CHK(fill<T>(LL.A.nrows, 0.0, *u2, D->stream));
             return relax_swap<T>(D, LL, ff, u2, sc);
         }
-        relax_zero_k<T><<<nblocks_d(LL.nrows), 256, 0, D->stream>>>(
-            LL.nrows, (const T *)LL.M, ff, *sc);
+        relax_zero_k<T><<<amg_nblocks(LL.A.nrows), 256, 0, D->stream>>>(
+            LL.A.nrows, (const T *)LL.M, ff, *sc);
         std::swap(*u2, *sc);
         return 0;
     };
 
     if (coarsest) {
         if (D->coarse_inv) {
-            CHK(gemv<T>(L.nrows, (const T *)D->coarse_inv, f, *u_io, D->stream));
+            CHK(gemv<T>(L.A.nrows, (const T *)D->coarse_inv, f, *u_io, D->stream));
         } else {
             for (int i = 0; i < D->npre + D->npost; ++i) {
                 if (u_is_zero && i == 0) {
@@ -313,7 +305,7 @@ static int cycle(Driver *D, int li, const T *f, T **u_io, T **scratch, bool u_is
     }
     // t = f - A u ; f_next = R t
     CHK(level_residual<T>(D, L, f, *u_io, *scratch));
-    CHK(transfer<T>(D, L, /*prolong=*/false, N.nrows, *scratch, 0.0, (T *)N.f));
+    CHK(op_spmv<T>(D, L.R, *scratch, 1.0, 0.0, (T *)N.f));
     T *nu = (T *)N.u;
     T *nscratch = (T *)N.t;
     for (int c = 0; c < D->ncycle; ++c) {
@@ -321,7 +313,7 @@ static int cycle(Driver *D, int li, const T *f, T **u_io, T **scratch, bool u_is
         // after the first sub-cycle the iterate is nonzero
     }
     // u += P u_next
-    CHK(transfer<T>(D, L, /*prolong=*/true, L.nrows, nu, 1.0, *u_io));
+    CHK(op_spmv<T>(D, L.P, nu, 1.0, 1.0, *u_io));
     for (int i = 0; i < D->npost; ++i)
         CHK(relax_swap<T>(D, L, f, u_io, scratch));
     return (int)hipGetLastError();
@@ -330,7 +322,7 @@ static int cycle(Driver *D, int li, const T *f, T **u_io, T **scratch, bool u_is
 // fp64 in/out preconditioner application; in f32 mode the V-cycle runs on the
 // fp32 hierarchy between two cast kernels (backend/detail/mixing.hpp shape)
 static int precond_apply(Driver *D, const double *rhs, double *x, double *x_swap) {
-    const int64_t n = D->lv[0].nrows;
+    const int64_t n = D->lv[0].A.nrows;
     if (D->f32) {
         CHK(amg_cast_d2s(n, rhs, D->cb_r, D->stream));
         float *u = D->cb_x;
@@ -407,11 +399,18 @@ static int read_dots(Driver *D, int n, double *out) {
 extern "C" void *amg_driver_create(const LevelDesc *levels, int nlevels,
                                    const void *coarse_inv, int64_t ncoarse, int npre,
                                    int npost, int ncycle, int pre_cycles, int f32,
-                                   int64_t a64_nnz, const int *a64_ptr,
-                                   const int *a64_col, const double *a64_val,
-                                   int a64_subw, hipStream_t stream) {
+                                   const OpDesc *a64, hipStream_t stream) {
+    if (f32 && !a64) return nullptr;
     Driver *D = new Driver();
     D->lv.assign(levels, levels + nlevels);
+    if (a64) D->a64 = *a64;
+    // settle every automatic CSR width once (relax_swap switches on it)
+    auto settle = [](OpDesc &op) {
+        if (op.subw <= 0) op.subw = amg_pick_subw(op.nrows, op.nnz);
+    };
+    settle(D->a64);
+    for (LevelDesc &L : D->lv)
+        for (OpDesc *op : {&L.A, &L.P, &L.R, &L.ilu_L, &L.ilu_U}) settle(*op);
     D->coarse_inv = coarse_inv;
     D->ncoarse = ncoarse;
     D->npre = npre;
@@ -420,11 +419,6 @@ extern "C" void *amg_driver_create(const LevelDesc *levels, int nlevels,
     D->pre_cycles = pre_cycles;
     D->stream = stream;
     D->f32 = f32;
-    D->a64_nnz = a64_nnz;
-    D->a64_ptr = a64_ptr;
-    D->a64_col = a64_col;
-    D->a64_val = a64_val;
-    D->a64_subw = a64_subw;
     D->cb_r = D->cb_x = D->cb_s = nullptr;
     const char *ng = getenv("AMGCL_NO_GRAPH");
     D->use_graphs = !(ng && ng[0] && ng[0] != '0');
@@ -442,7 +436,7 @@ extern "C" void *amg_driver_create(const LevelDesc *levels, int nlevels,
     bool ok = hipMalloc((void **)&D->dotbuf_d, 2 * sizeof(double)) == hipSuccess &&
               hipHostMalloc((void **)&D->dotbuf_h, 2 * sizeof(double)) == hipSuccess;
     if (ok && f32) {
-        int64_t n = D->lv[0].nrows;
+        int64_t n = D->lv[0].A.nrows;
         ok = hipMalloc((void **)&D->cb_r, n * sizeof(float)) == hipSuccess &&
              hipMalloc((void **)&D->cb_x, n * sizeof(float)) == hipSuccess &&
              hipMalloc((void **)&D->cb_s, n * sizeof(float)) == hipSuccess;
@@ -469,10 +463,27 @@ extern "C" void amg_driver_destroy(void *h) {
     delete D;
 }
 
-// LevelDesc layout as compiled, for the ctypes twin (backend/native.py
-// LevelDescC) to check itself against when it binds
-extern "C" int amg_leveldesc_size() { return (int)sizeof(LevelDesc); }
-extern "C" int amg_leveldesc_last_offset() { return (int)offsetof(LevelDesc, ilu_b); }
+// OpDesc / LevelDesc layout as compiled, for the ctypes twins (backend/
+// native.py) to check themselves against when they bind: both sizes, then
+// the offset of every OpDesc member and of every top-level LevelDesc member
+// in declaration order.  Writes at most cap entries, returns the full count.
+extern "C" int amg_desc_layout(int64_t *out, int cap) {
+#define OP(m) offsetof(OpDesc, m)
+#define LV(m) offsetof(LevelDesc, m)
+    const size_t v[] = {
+        sizeof(OpDesc), sizeof(LevelDesc),
+        OP(nrows), OP(nnz), OP(ptr), OP(col), OP(val), OP(subw), OP(nslice), OP(soff), OP(scol),
+        OP(sval), OP(srows),
+        LV(A), LV(P), LV(R), LV(M), LV(f), LV(u), LV(t), LV(cheb_degree), LV(cheb_theta),
+        LV(cheb_delta), LV(cheb_sigma1), LV(cheb_d), LV(bsize), LV(nbrows), LV(bptr), LV(bcol),
+        LV(bval), LV(ilu_iters), LV(ilu_damping), LV(ilu_jdamping), LV(ilu_L), LV(ilu_U),
+        LV(ilu_dinv), LV(ilu_y), LV(ilu_s), LV(ilu_b)};
+#undef OP
+#undef LV
+    const int count = (int)(sizeof v / sizeof v[0]);
+    for (int i = 0; i < count && i < cap; ++i) out[i] = (int64_t)v[i];
+    return count;
+}
 
 // The single exit of every entry point once enter_driver has succeeded; rc
 // is what the body returned (0, a failed launch, a BiCGStab breakdown).  The
@@ -494,36 +505,26 @@ extern "C" int amg_driver_precond(void *h, const double *rhs, double *x, double 
     return finish(D, precond_apply_graphed(D, rhs, x, x_swap), /*sync=*/false);
 }
 
-// The fp64 fine operator the Krylov loops iterate with: level 0, or in mixed
-// mode the a64_* CSR copy (level 0 then describes the fp32 operator the cycle
-// runs on, which has no fp64 SELL or BSR image)
+// The fp64 fine operator the Krylov loops iterate with: level 0's A, or in
+// mixed mode the fp64 copy (level 0 then describes the fp32 operator the
+// cycle runs on, which has no BSR form)
 struct FineOp {
     Driver *D;
-    LevelDesc L;
-    explicit FineOp(Driver *D) : D(D), L(D->lv[0]) {
-        if (!D->f32) return;
-        L.nnz = D->a64_nnz;
-        L.ptr = D->a64_ptr;
-        L.col = D->a64_col;
-        L.val = D->a64_val;
-        L.subw = D->a64_subw;
-        L.nslice = 0;
-        L.bsize = 0;
-    }
+    OpDesc op;
+    const LevelDesc *bsr;  // level 0 when it stores A as BSR, else null
+    explicit FineOp(Driver *D)
+        : D(D), op(D->f32 ? D->a64 : D->lv[0].A),
+          bsr(!D->f32 && D->lv[0].bsize ? &D->lv[0] : nullptr) {}
     // y = alpha A x + beta y, storage precedence as in level_residual
     int spmv(const double *x, double alpha, double beta, double *y) const {
-        if (L.bsize)
-            return amg_bsr_spmv_f64(L.nbrows, L.bsize, L.bptr, L.bcol, L.bval, x, alpha,
-                                    beta, y, D->stream);
-        if (L.nslice)
-            return amg_sell_spmv_f64(L.nrows, L.nslice, L.soff, L.scol,
-                                     (const double *)L.sval, L.srows, x, alpha, beta, y,
-                                     D->stream);
-        return amg_spmv_f64(L.nrows, L.nnz, L.ptr, L.col, L.val, x, alpha, beta, y,
-                            L.subw, D->stream);
+        if (bsr)
+            return amg_bsr_spmv_f64(bsr->nbrows, bsr->bsize, bsr->bptr, bsr->bcol,
+                                    bsr->bval, x, alpha, beta, y, D->stream);
+        return op_spmv<double>(D, op, x, alpha, beta, y);
     }
     int residual(const double *rhs, const double *x, double *r) const {
-        return level_residual<double>(D, L, rhs, x, r);
+        return bsr ? level_residual<double>(D, *bsr, rhs, x, r)
+                   : op_residual<double>(D, op, rhs, x, r);
     }
 };
 
@@ -537,7 +538,7 @@ struct Krylov {
 static int krylov_begin(Driver *D, const FineOp &A, const double *rhs, double *x,
                         double *r, double *r_copy, double tol, double abstol,
                         Krylov *k) {
-    const int64_t n = A.L.nrows;
+    const int64_t n = A.op.nrows;
     hipStream_t st = D->stream;
     double dot;
     CHK(amg_dot_f64(n, rhs, rhs, D->dotbuf_d, st));
@@ -569,7 +570,7 @@ static int cg_solve(Driver *D, const double *rhs, double *x, double *r, double *
                     double *p, double *q, double *s_swap, double tol, double abstol,
                     int maxiter, int64_t *iters_out, double *resid_out) {
     const FineOp A(D);
-    const int64_t n = A.L.nrows;
+    const int64_t n = A.op.nrows;
     hipStream_t st = D->stream;
     double dots[2];
     Krylov k;
@@ -619,7 +620,7 @@ static int bicgstab_solve(Driver *D, const double *rhs, double *x, double *r, do
                           double *T_swap, double tol, double abstol, int maxiter,
                           int64_t *iters_out, double *resid_out) {
     const FineOp A(D);
-    const int64_t n = A.L.nrows;
+    const int64_t n = A.op.nrows;
     hipStream_t st = D->stream;
     double dots[2];
     Krylov k;

@@ -90,19 +90,10 @@ __global__ void relax_diag_k(int nrows, const int *__restrict__ ptr,
     }
 }
 
-static inline int pick_subw(int64_t nrows, int64_t nnz) {
-    double m = nrows ? (double)nnz / (double)nrows : 1.0;
-    if (m <= 4) return 2;
-    if (m <= 10) return 4;
-    if (m <= 24) return 8;
-    if (m <= 128) return 16;
-    return 32;
-}
-
 extern "C" int amg_spmv_f64(int64_t nrows, int64_t nnz, const int *ptr, const int *col,
                             const double *val, const double *x, double alpha,
                             double beta, double *y, int subw, hipStream_t stream) {
-    if (subw <= 0) subw = pick_subw(nrows, nnz);
+    if (subw <= 0) subw = amg_pick_subw(nrows, nnz);
     int grid = nblocks(nrows * subw);
     const int B = 256;
 #define CASE(SW)                                                                    \
@@ -123,7 +114,7 @@ extern "C" int amg_spmv_f64(int64_t nrows, int64_t nnz, const int *ptr, const in
 extern "C" int amg_residual_f64(int64_t nrows, int64_t nnz, const int *ptr, const int *col,
                                 const double *val, const double *rhs, const double *x,
                                 double *r, int subw, hipStream_t stream) {
-    if (subw <= 0) subw = pick_subw(nrows, nnz);
+    if (subw <= 0) subw = amg_pick_subw(nrows, nnz);
     int grid = nblocks(nrows * subw);
     const int B = 256;
 #define CASE(SW)                                                                    \
@@ -142,7 +133,7 @@ extern "C" int amg_relax_diag_f64(int64_t nrows, int64_t nnz, const int *ptr,
                                   const int *col, const double *val, const double *M,
                                   const double *rhs, const double *x, double *t,
                                   int subw, hipStream_t stream) {
-    if (subw <= 0) subw = pick_subw(nrows, nnz);
+    if (subw <= 0) subw = amg_pick_subw(nrows, nnz);
     int grid = nblocks(nrows * subw);
     const int B = 256;
 #define CASE(SW)                                                                       \
@@ -600,7 +591,7 @@ extern "C" int amg_gemv_f64(int64_t n, const double *a, const double *f, double 
 extern "C" int amg_spmv_f32(int64_t nrows, int64_t nnz, const int *ptr, const int *col,
                             const float *val, const float *x, double alpha, double beta,
                             float *y, int subw, hipStream_t stream) {
-    if (subw <= 0) subw = pick_subw(nrows, nnz);
+    if (subw <= 0) subw = amg_pick_subw(nrows, nnz);
     int grid = nblocks(nrows * subw);
 #define CASE(SW)                                                                        \
     case SW:                                                                            \
@@ -622,7 +613,7 @@ extern "C" int amg_spmv_f32(int64_t nrows, int64_t nnz, const int *ptr, const in
 extern "C" int amg_residual_f32(int64_t nrows, int64_t nnz, const int *ptr, const int *col,
                                 const float *val, const float *rhs, const float *x,
                                 float *r, int subw, hipStream_t stream) {
-    if (subw <= 0) subw = pick_subw(nrows, nnz);
+    if (subw <= 0) subw = amg_pick_subw(nrows, nnz);
     int grid = nblocks(nrows * subw);
 #define CASE(SW)                                                                      \
     case SW:                                                                          \
@@ -640,7 +631,7 @@ extern "C" int amg_relax_diag_f32(int64_t nrows, int64_t nnz, const int *ptr,
                                   const int *col, const float *val, const float *M,
                                   const float *rhs, const float *x, float *t, int subw,
                                   hipStream_t stream) {
-    if (subw <= 0) subw = pick_subw(nrows, nnz);
+    if (subw <= 0) subw = amg_pick_subw(nrows, nnz);
     int grid = nblocks(nrows * subw);
 #define CASE(SW)                                                                          \
     case SW:                                                                              \
@@ -845,7 +836,7 @@ static int cspmv_dispatch(int64_t nrows, int64_t nnz, const int *ptr, const int 
                           const void *val, const void *x, c128 a, c128 b,
                           const void *rhs, const void *M, void *y, int subw, int mode,
                           hipStream_t stream) {
-    if (subw <= 0) subw = pick_subw(nrows, nnz);
+    if (subw <= 0) subw = amg_pick_subw(nrows, nnz);
 #define CC(SW)                                                                      \
     case SW:                                                                        \
         if (mode == 0) CSPMV_LAUNCH(SW, 0);                                         \

@@ -327,6 +327,87 @@ print("DEVICE_SETUP_OK", it.value, it2.value, res.value)
     assert "DEVICE_SETUP_OK" in out
 
 
+@pytest.mark.gpu
+def test_torch_free_gpu_device_setup_sell(tmp_path):
+    """The SELL-64 fill of the torch-free device setup at a few thousand
+    rows: Poisson 33^3 (35937 rows, not a multiple of 64, so the last slice
+    is partial), two device-built levels, solved with SELL images on every
+    device-built operator (precond.sell_min_rows=1), with none
+    (sell_min_rows above n) and with the host setup.  The two device runs
+    differ only in the storage the kernels read."""
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    A, _ = am.poisson3d(33)
+    assert A.nrows == 35937 and A.nrows % 64 != 0
+    npz = str(tmp_path / "a33.npz")
+    np.savez(npz, ptr=np.asarray(A.ptr, dtype=np.int32),
+             col=np.asarray(A.col, dtype=np.int32),
+             val=np.asarray(A.val, dtype=np.float64))
+    prog = r"""
+import ctypes, sys
+import numpy as np
+d = np.load(r"%s")
+ptr, col, val = d["ptr"], d["col"], d["val"]
+n = len(ptr) - 1
+lib = ctypes.CDLL(r"%s/amgcl_amd/_hip/libamghip.so")
+lib.amgcl_amd_gpu_solver_create.restype = ctypes.c_void_p
+lib.amgcl_amd_gpu_solver_create.argtypes = [ctypes.c_int] + [ctypes.c_void_p]*3 + [ctypes.c_char_p]
+lib.amgcl_amd_gpu_solver_solve.restype = ctypes.c_int
+lib.amgcl_amd_gpu_solver_solve.argtypes = [ctypes.c_void_p]*3 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
+lib.amgcl_amd_gpu_solver_destroy.argtypes = [ctypes.c_void_p]
+b = np.ones(n)
+base = "solver.type=cg;solver.tol=1e-8;precond.coarse_enough=500;precond.device_handoff=1000;"
+def run(name, extra):
+    print("RUN", name, flush=True)
+    h = lib.amgcl_amd_gpu_solver_create(n, ptr.ctypes.data, col.ctypes.data,
+                                        val.ctypes.data, (base + extra).encode())
+    assert h, "create failed"
+    x = np.zeros(n); it = ctypes.c_int(0); res = ctypes.c_double(0.0)
+    rc = lib.amgcl_amd_gpu_solver_solve(h, b.ctypes.data, x.ctypes.data,
+                                        ctypes.byref(it), ctypes.byref(res))
+    lib.amgcl_amd_gpu_solver_destroy(h)
+    assert rc == 0, (name, rc)
+    assert res.value < 1e-8, (name, res.value)
+    return x, it.value
+xs, its = run("sell", "precond.setup=device;precond.sell_min_rows=1")
+xc, itc = run("csr", "precond.setup=device;precond.sell_min_rows=%%d" %% (n + 1))
+xh, ith = run("host", "precond.setup=host")
+diff = np.linalg.norm(xs - xc) / np.linalg.norm(xc)
+err = np.abs(xs - xh).max() / np.abs(xh).max()
+print("FIGURES iters sell/csr/host", its, itc, ith, "sell-vs-csr", diff,
+      "device-vs-host", err, flush=True)
+assert its == itc, (its, itc)
+assert diff < 1e-8, diff
+# device against host setup: the bounds of test_torch_free_gpu_device_setup
+assert abs(its - ith) <= 3, (its, ith)
+assert err < 1e-6, err
+assert "torch" not in sys.modules
+print("SELL_SETUP_OK", flush=True)
+""" % (npz, root)
+    env = dict(os.environ, AMGCL_CAPI_TRACE="1")
+    out = subprocess.check_output([sys.executable, "-c", prog], text=True, env=env,
+                                  stderr=subprocess.STDOUT, timeout=300)
+    print(out)
+    assert "SELL_SETUP_OK" in out
+    # the setup trace: two device-built levels in each device run and none
+    # in the host run; "sell <A slices> <P slices>" per device-built level
+    runs = {}
+    for chunk in out.split("RUN ")[1:]:
+        name, _, body = chunk.partition("\n")
+        runs[name.strip()] = body
+    count = lambda name, what: runs[name].count("[capi setup] %s " % what)
+    assert count("sell", "record") == 2 and count("csr", "record") == 2
+    assert count("host", "record") == 0
+    nslice = (A.nrows + 63) // 64
+    assert "[capi setup] sell %d %d\n" % (nslice, nslice) in runs["sell"]
+    assert runs["sell"].count("[capi setup] sell 0") == 0
+    assert runs["csr"].count("[capi setup] sell 0 0\n") == 2
+
+
 def test_capi_rejects_unknown_solver(capi):
     """The compiled engine carries CG/BiCGStab; asking for anything else
     must fail at create (NULL handle), never silently substitute."""

@@ -243,6 +243,8 @@ def _storage_case(storage, solver):
         if storage == "sell":
             precond.update({"sell": "auto", "sell_min_rows": 1,
                             "sell_min_mean": 0.0})
+        elif storage == "sell_sigma":
+            precond["sell"] = "off"  # the test builds the sigma-sorted images
         elif storage == "mixed":
             precond = {"class": "amg", "precision": "mixed"}
         tol, maxiter = 1e-8, 100
@@ -251,20 +253,36 @@ def _storage_case(storage, solver):
     return A, b, prm, tol
 
 
-@pytest.mark.parametrize("storage", ["csr", "sell", "bsr", "mixed"])
+def _sigma_sell_images(s):
+    """Give A, P and R of every level a sigma-sorted SELL image (the sort's
+    size and padding gates lowered so it engages at test size), then attach a
+    fresh native driver that sees them."""
+    from amgcl_amd.backend.native import try_native
+
+    ops = [M for l in s.P.levels for M in (l.A, l.P, l.R) if M is not None]
+    for M in ops:
+        M.build_sell(sigma=128, sigma_min_rows=0, sigma_min_pad=0.0)
+        assert M.nslice and M.srows is not None
+    assert len(ops) == 3 * len(s.P.levels) - 2 and len(s.P.levels) >= 2
+    s._native = try_native(s)
+
+
+@pytest.mark.parametrize("storage", ["csr", "sell", "bsr", "mixed", "sell_sigma"])
 @pytest.mark.parametrize("solver", ["cg", "bicgstab"])
 def test_native_storage_matrix(hip, solver, storage):
     """Both native Krylov loops against the generic path for every storage
     the fine operator can carry (CSR, SELL, BSR, fp64 override of a mixed
-    hierarchy)."""
+    hierarchy, SELL with sigma-sorted rows on A, P and R)."""
     from amgcl_amd.backend.hip import DeviceBSR
 
     A, b, prm, tol = _storage_case(storage, solver)
     s = am.make_solver(A, prm, backend=hip)
+    if storage == "sell_sigma":
+        _sigma_sell_images(s)
     assert s._native is not None, "native driver should engage for this config"
     A0 = s.P.levels[0].A
     assert isinstance(A0, DeviceBSR) == (storage == "bsr")
-    assert bool(getattr(A0, "nslice", 0)) == (storage == "sell")
+    assert bool(getattr(A0, "nslice", 0)) == (storage in ("sell", "sell_sigma"))
     assert s._native._mixed == (storage == "mixed")
     x1, it1, res1 = s(b)
 
@@ -299,15 +317,24 @@ def test_native_zero_rhs(hip, solver):
 
 
 def test_leveldesc_layout():
-    """The ctypes LevelDescC and the compiled LevelDesc agree on the struct's
-    size and on the offset of its last field (what _bind() enforces)."""
+    """The ctypes OpDescC / LevelDescC and the compiled structs agree on both
+    sizes and on the offset of every OpDesc member and every top-level
+    LevelDesc member (what _bind() enforces)."""
     import ctypes
 
     from amgcl_amd.backend import native
 
     L = native._bind()
-    assert L.amg_leveldesc_size() == ctypes.sizeof(native.LevelDescC)
-    assert L.amg_leveldesc_last_offset() == native.LevelDescC.ilu_b.offset
+    ours = native.desc_layout()
+    assert [label for label, _ in ours[:2]] == ["sizeof(OpDesc)", "sizeof(LevelDesc)"]
+    assert len(ours) == 2 + len(native.OpDescC._fields_) + len(native.LevelDescC._fields_)
+    assert ours[0][1] == ctypes.sizeof(native.OpDescC)
+    assert ours[1][1] == ctypes.sizeof(native.LevelDescC)
+    assert ours[-1] == ("offsetof(LevelDesc, ilu_b)", native.LevelDescC.ilu_b.offset)
+    theirs = native.lib_desc_layout(L)
+    assert len(theirs) == len(ours)
+    for (label, mine), lib_value in zip(ours, theirs):
+        assert mine == lib_value, label
 
 
 @pytest.mark.gpu
