@@ -37,27 +37,7 @@ _SIGS = {
                         ctypes.c_void_p],
     "amg_gemv_f64": [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                      ctypes.c_void_p],
-    # --- fp32 variants (mixed precision) + casts ---
-    "amg_spmv_f32": [ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double,
-                     ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
-    "amg_residual_f32": [ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                         ctypes.c_int, ctypes.c_void_p],
-    "amg_relax_diag_f32": [ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                           ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
-    "amg_axpby_f32": [ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_double,
-                      ctypes.c_void_p, ctypes.c_void_p],
-    "amg_axpbypcz_f32": [ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_double,
-                         ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p],
-    "amg_vmul_f32": [ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
-                     ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p],
-    "amg_fill_f32": [ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p],
-    "amg_dot_f32": [ctypes.c_int64] + [ctypes.c_void_p] * 4,
-    "amg_gather_f32": [ctypes.c_int64] + [ctypes.c_void_p] * 4,
-    "amg_scatter_f32": [ctypes.c_int64] + [ctypes.c_void_p] * 4,
-    "amg_gemv_f32": [ctypes.c_int64] + [ctypes.c_void_p] * 4,
+    # --- precision casts (mixed-precision boundary) ---
     "amg_cast_d2s": [ctypes.c_int64] + [ctypes.c_void_p] * 3,
     "amg_cast_s2d": [ctypes.c_int64] + [ctypes.c_void_p] * 3,
     "amg_gs_color_f64": [ctypes.c_int64] + [ctypes.c_void_p] * 7,
@@ -100,12 +80,6 @@ _SIGS = {
     "amg_sell_residual_f64": [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 8,
     "amg_sell_relax_f64": [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 9,
     "amg_sell_fill_f64": [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 8,
-    "amg_sell_spmv_f32": [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 5
-                         + [ctypes.c_double, ctypes.c_double]
-                         + [ctypes.c_void_p] * 2,
-    "amg_sell_residual_f32": [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 8,
-    "amg_sell_relax_f32": [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 9,
-    "amg_sell_fill_f32": [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 8,
     # --- block (BSR) solve kernels ---
     "amg_bsr_spmv_f64": [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
@@ -144,6 +118,13 @@ _SIGS = {
     "amg_poisson_cnt": [ctypes.c_int64] * 4 + [ctypes.c_void_p] * 2,
     "amg_poisson_fill": [ctypes.c_int64] * 4 + [ctypes.c_void_p] * 4,
 }
+
+# fp32 twins (mixed precision): pointers cross as void*, so each takes exactly
+# the ctypes arguments of its _f64 entry above
+for _op in ("spmv", "residual", "relax_diag", "axpby", "axpbypcz", "vmul", "fill", "dot",
+            "gather", "scatter", "gemv", "sell_spmv", "sell_residual", "sell_relax",
+            "sell_fill"):
+    _SIGS[f"amg_{_op}_f32"] = _SIGS[f"amg_{_op}_f64"]
 
 
 def lib():

@@ -55,6 +55,20 @@ class DeviceCSR:
     def nnz(self):
         return self.col.numel()
 
+    @property
+    def csr_args(self):
+        """Leading arguments of the CSR kernels: nrows, nnz, ptr, col, val."""
+        return (self.nrows, self.nnz, self.ptr.data_ptr(), self.col.data_ptr(),
+                self.val.data_ptr())
+
+    @property
+    def sell_args(self):
+        """Leading arguments of the SELL kernels: nrows, nslice, soff, scol,
+        sval, srows (0 without a sigma-sort permutation)."""
+        return (self.nrows, self.nslice, self.soff.data_ptr(), self.scol.data_ptr(),
+                self.sval.data_ptr(),
+                self.srows.data_ptr() if self.srows is not None else 0)
+
     def bytes(self):
         b = (self.ptr.numel() + self.col.numel()) * 4 + self.val.numel() * 8
         if self.nslice:
@@ -179,6 +193,12 @@ class DeviceBSR:
     def nnz(self):
         return self.val.numel()
 
+    @property
+    def bsr_args(self):
+        """Leading arguments of the BSR kernels: nbrows, bsize, ptr, col, val."""
+        return (self.nbrows, self.bsize, self.ptr.data_ptr(), self.col.data_ptr(),
+                self.val.data_ptr())
+
     @classmethod
     def from_device(cls, dcsr, bsize, device):
         """Convert a device CSR to BSR entirely on the GPU (torch ops): the
@@ -268,88 +288,51 @@ class HipBackend:
 
     def spmv(self, alpha, A, x, beta, y):
         if isinstance(A, DeviceBSR):
-            check(lib().amg_bsr_spmv_f64(A.nbrows, A.bsize, A.ptr.data_ptr(),
-                                         A.col.data_ptr(), A.val.data_ptr(),
-                                         x.data_ptr(), alpha, beta, y.data_ptr(),
-                                         _stream()), "bsr_spmv")
-            return
-        if A.val.is_complex():
+            check(lib().amg_bsr_spmv_f64(*A.bsr_args, x.data_ptr(), alpha, beta,
+                                         y.data_ptr(), _stream()), "bsr_spmv")
+        elif A.val.is_complex():
             a, b = complex(alpha), complex(beta)
-            check(lib().amg_spmv_c128(A.nrows, A.nnz, A.ptr.data_ptr(),
-                                      A.col.data_ptr(), A.val.data_ptr(),
-                                      x.data_ptr(), a.real, a.imag, b.real, b.imag,
-                                      y.data_ptr(), A.subw, _stream()), "cspmv")
-            return
-        if getattr(A, "nslice", 0):
-            check(self._fn("sell_spmv", A.sval)(A.nrows, A.nslice, A.soff.data_ptr(),
-                                                A.scol.data_ptr(), A.sval.data_ptr(),
-                                                A.srows.data_ptr() if A.srows is not None else 0,
-                                                x.data_ptr(), alpha, beta,
+            check(lib().amg_spmv_c128(*A.csr_args, x.data_ptr(), a.real, a.imag, b.real,
+                                      b.imag, y.data_ptr(), A.subw, _stream()), "cspmv")
+        elif getattr(A, "nslice", 0):
+            check(self._fn("sell_spmv", A.sval)(*A.sell_args, x.data_ptr(), alpha, beta,
                                                 y.data_ptr(), _stream()), "sell_spmv")
-            return
-        check(self._fn("spmv", A.val)(A.nrows, A.nnz, A.ptr.data_ptr(), A.col.data_ptr(),
-                                      A.val.data_ptr(), x.data_ptr(), alpha, beta,
-                                      y.data_ptr(), A.subw, _stream()), "spmv")
+        else:
+            check(self._fn("spmv", A.val)(*A.csr_args, x.data_ptr(), alpha, beta,
+                                          y.data_ptr(), A.subw, _stream()), "spmv")
 
     def residual(self, b, A, x, r):
+        vecs = (b.data_ptr(), x.data_ptr(), r.data_ptr())
         if isinstance(A, DeviceBSR):
-            check(lib().amg_bsr_residual_f64(A.nbrows, A.bsize, A.ptr.data_ptr(),
-                                             A.col.data_ptr(), A.val.data_ptr(),
-                                             b.data_ptr(), x.data_ptr(), r.data_ptr(),
-                                             _stream()), "bsr_residual")
-            return
-        if A.val.is_complex():
-            check(lib().amg_residual_c128(A.nrows, A.nnz, A.ptr.data_ptr(),
-                                          A.col.data_ptr(), A.val.data_ptr(),
-                                          b.data_ptr(), x.data_ptr(), r.data_ptr(),
-                                          A.subw, _stream()), "cresidual")
-            return
-        if getattr(A, "nslice", 0):
-            check(self._fn("sell_residual", A.sval)(A.nrows, A.nslice,
-                                                    A.soff.data_ptr(), A.scol.data_ptr(),
-                                                    A.sval.data_ptr(),
-                                                    A.srows.data_ptr() if A.srows is not None else 0,
-                                                    b.data_ptr(),
-                                                    x.data_ptr(), r.data_ptr(),
-                                                    _stream()), "sell_residual")
-            return
-        check(self._fn("residual", A.val)(A.nrows, A.nnz, A.ptr.data_ptr(),
-                                          A.col.data_ptr(), A.val.data_ptr(),
-                                          b.data_ptr(), x.data_ptr(), r.data_ptr(),
-                                          A.subw, _stream()), "residual")
+            check(lib().amg_bsr_residual_f64(*A.bsr_args, *vecs, _stream()),
+                  "bsr_residual")
+        elif A.val.is_complex():
+            check(lib().amg_residual_c128(*A.csr_args, *vecs, A.subw, _stream()),
+                  "cresidual")
+        elif getattr(A, "nslice", 0):
+            check(self._fn("sell_residual", A.sval)(*A.sell_args, *vecs, _stream()),
+                  "sell_residual")
+        else:
+            check(self._fn("residual", A.val)(*A.csr_args, *vecs, A.subw, _stream()),
+                  "residual")
 
     def relax_diag(self, A, M, rhs, x, t):
         """t = M∘(rhs - A x); x += t (fused single pass over A + axpby)."""
+        vecs = (M.data_ptr(), rhs.data_ptr(), x.data_ptr(), t.data_ptr())
         if isinstance(A, DeviceBSR):
-            check(lib().amg_bsr_relax_f64(A.nbrows, A.bsize, A.ptr.data_ptr(),
-                                          A.col.data_ptr(), A.val.data_ptr(),
-                                          M.data_ptr(), rhs.data_ptr(), x.data_ptr(),
-                                          t.data_ptr(), _stream()), "bsr_relax")
-            self.axpby(1.0, t, 1.0, x)
-            return
-        if A.val.is_complex():
-            check(lib().amg_relax_diag_c128(A.nrows, A.nnz, A.ptr.data_ptr(),
-                                            A.col.data_ptr(), A.val.data_ptr(),
-                                            M.data_ptr(), rhs.data_ptr(),
-                                            x.data_ptr(), t.data_ptr(), A.subw,
-                                            _stream()), "crelax")
-            self.axpby(1.0, t, 1.0, x)
-            return
-        if getattr(A, "nslice", 0):
+            check(lib().amg_bsr_relax_f64(*A.bsr_args, *vecs, _stream()), "bsr_relax")
+        elif A.val.is_complex():
+            check(lib().amg_relax_diag_c128(*A.csr_args, *vecs, A.subw, _stream()),
+                  "crelax")
+        elif getattr(A, "nslice", 0):
             # SELL relax writes x_new = x + M(rhs - Ax) into t, then copy back
-            check(self._fn("sell_relax", A.sval)(A.nrows, A.nslice, A.soff.data_ptr(),
-                                                 A.scol.data_ptr(), A.sval.data_ptr(),
-                                                 A.srows.data_ptr() if A.srows is not None else 0,
-                                                 M.data_ptr(), rhs.data_ptr(),
-                                                 x.data_ptr(), t.data_ptr(),
-                                                 _stream()), "sell_relax")
+            check(self._fn("sell_relax", A.sval)(*A.sell_args, *vecs, _stream()),
+                  "sell_relax")
             x.copy_(t)
             return
-        check(self._fn("relax_diag", A.val)(A.nrows, A.nnz, A.ptr.data_ptr(),
-                                            A.col.data_ptr(), A.val.data_ptr(),
-                                            M.data_ptr(), rhs.data_ptr(), x.data_ptr(),
-                                            t.data_ptr(), A.subw, _stream()),
-              "relax_diag")
+        else:
+            check(self._fn("relax_diag", A.val)(*A.csr_args, *vecs, A.subw, _stream()),
+                  "relax_diag")
         self.axpby(1.0, t, 1.0, x)
 
     def clear(self, x):

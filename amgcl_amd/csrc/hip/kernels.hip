@@ -15,13 +15,13 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 #include "amg_common.h"
 #include "amg_kernels.h"
 
-static inline int nblocks(int64_t work, int block = 256, int cap = 2048) {
-    return amg_nblocks(work, block, cap);
-}
+// Every launcher below is written once as a template over the value type
+// (launch_*<T>); the extern "C" _f64/_f32 entry points only forward to it.
 
 extern "C" int amg_hip_last_error() { return (int)hipGetLastError(); }
 
@@ -90,18 +90,16 @@ __global__ void relax_diag_k(int nrows, const int *__restrict__ ptr,
     }
 }
 
-extern "C" int amg_spmv_f64(int64_t nrows, int64_t nnz, const int *ptr, const int *col,
-                            const double *val, const double *x, double alpha,
-                            double beta, double *y, int subw, hipStream_t stream) {
+// The one place a runtime sub-wave width becomes a template argument:
+// launch(std::integral_constant<int, SW>) for the widths the row kernels are
+// instantiated for, hipErrorInvalidValue for any other.  subw <= 0 picks the
+// width from the mean row length.
+template <typename F>
+static int by_subw(int subw, int64_t nrows, int64_t nnz, F launch) {
     if (subw <= 0) subw = amg_pick_subw(nrows, nnz);
-    int grid = nblocks(nrows * subw);
-    const int B = 256;
-#define CASE(SW)                                                                    \
-    case SW:                                                                        \
-        if (beta == 0.0)                                                            \
-            spmv_k<double, SW, true><<<grid, B, 0, stream>>>(nrows, ptr, col, val, x, alpha, beta, y);  \
-        else                                                                        \
-            spmv_k<double, SW, false><<<grid, B, 0, stream>>>(nrows, ptr, col, val, x, alpha, beta, y); \
+#define CASE(SW)                                     \
+    case SW:                                         \
+        launch(std::integral_constant<int, SW>{});   \
         break;
     switch (subw) {
         CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
@@ -111,41 +109,75 @@ extern "C" int amg_spmv_f64(int64_t nrows, int64_t nnz, const int *ptr, const in
     return (int)hipGetLastError();
 }
 
+template <typename T>
+static int launch_spmv(int64_t nrows, int64_t nnz, const int *ptr, const int *col,
+                       const T *val, const T *x, double alpha, double beta, T *y,
+                       int subw, hipStream_t stream) {
+    return by_subw(subw, nrows, nnz, [&](auto sw) {
+        constexpr int SW = decltype(sw)::value;
+        const int grid = amg_nblocks(nrows * SW);
+        if (beta == 0.0)
+            spmv_k<T, SW, true><<<grid, 256, 0, stream>>>(nrows, ptr, col, val, x, alpha, beta, y);
+        else
+            spmv_k<T, SW, false><<<grid, 256, 0, stream>>>(nrows, ptr, col, val, x, alpha, beta, y);
+    });
+}
+
+template <typename T>
+static int launch_residual(int64_t nrows, int64_t nnz, const int *ptr, const int *col,
+                           const T *val, const T *rhs, const T *x, T *r, int subw,
+                           hipStream_t stream) {
+    return by_subw(subw, nrows, nnz, [&](auto sw) {
+        constexpr int SW = decltype(sw)::value;
+        residual_k<T, SW><<<amg_nblocks(nrows * SW), 256, 0, stream>>>(nrows, ptr, col, val,
+                                                                      rhs, x, r);
+    });
+}
+
+template <typename T>
+static int launch_relax_diag(int64_t nrows, int64_t nnz, const int *ptr, const int *col,
+                             const T *val, const T *M, const T *rhs, const T *x, T *t,
+                             int subw, hipStream_t stream) {
+    return by_subw(subw, nrows, nnz, [&](auto sw) {
+        constexpr int SW = decltype(sw)::value;
+        relax_diag_k<T, SW><<<amg_nblocks(nrows * SW), 256, 0, stream>>>(nrows, ptr, col,
+                                                                        val, M, rhs, x, t);
+    });
+}
+
+extern "C" int amg_spmv_f64(int64_t nrows, int64_t nnz, const int *ptr, const int *col,
+                            const double *val, const double *x, double alpha,
+                            double beta, double *y, int subw, hipStream_t stream) {
+    return launch_spmv(nrows, nnz, ptr, col, val, x, alpha, beta, y, subw, stream);
+}
+extern "C" int amg_spmv_f32(int64_t nrows, int64_t nnz, const int *ptr, const int *col,
+                            const float *val, const float *x, double alpha, double beta,
+                            float *y, int subw, hipStream_t stream) {
+    return launch_spmv(nrows, nnz, ptr, col, val, x, alpha, beta, y, subw, stream);
+}
+
 extern "C" int amg_residual_f64(int64_t nrows, int64_t nnz, const int *ptr, const int *col,
                                 const double *val, const double *rhs, const double *x,
                                 double *r, int subw, hipStream_t stream) {
-    if (subw <= 0) subw = amg_pick_subw(nrows, nnz);
-    int grid = nblocks(nrows * subw);
-    const int B = 256;
-#define CASE(SW)                                                                    \
-    case SW:                                                                        \
-        residual_k<double, SW><<<grid, B, 0, stream>>>(nrows, ptr, col, val, rhs, x, r);    \
-        break;
-    switch (subw) {
-        CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef CASE
-    return (int)hipGetLastError();
+    return launch_residual(nrows, nnz, ptr, col, val, rhs, x, r, subw, stream);
+}
+extern "C" int amg_residual_f32(int64_t nrows, int64_t nnz, const int *ptr, const int *col,
+                                const float *val, const float *rhs, const float *x,
+                                float *r, int subw, hipStream_t stream) {
+    return launch_residual(nrows, nnz, ptr, col, val, rhs, x, r, subw, stream);
 }
 
 extern "C" int amg_relax_diag_f64(int64_t nrows, int64_t nnz, const int *ptr,
                                   const int *col, const double *val, const double *M,
                                   const double *rhs, const double *x, double *t,
                                   int subw, hipStream_t stream) {
-    if (subw <= 0) subw = amg_pick_subw(nrows, nnz);
-    int grid = nblocks(nrows * subw);
-    const int B = 256;
-#define CASE(SW)                                                                       \
-    case SW:                                                                           \
-        relax_diag_k<double, SW><<<grid, B, 0, stream>>>(nrows, ptr, col, val, M, rhs, x, t);  \
-        break;
-    switch (subw) {
-        CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef CASE
-    return (int)hipGetLastError();
+    return launch_relax_diag(nrows, nnz, ptr, col, val, M, rhs, x, t, subw, stream);
+}
+extern "C" int amg_relax_diag_f32(int64_t nrows, int64_t nnz, const int *ptr,
+                                  const int *col, const float *val, const float *M,
+                                  const float *rhs, const float *x, float *t, int subw,
+                                  hipStream_t stream) {
+    return launch_relax_diag(nrows, nnz, ptr, col, val, M, rhs, x, t, subw, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -197,63 +229,59 @@ __global__ void sell_k(int64_t nrows, int64_t nslice,
     }
 }
 
-#define SELL_LAUNCH(T, MODE, ...)                                                   \
-    sell_k<T, MODE><<<nblocks(nslice * WAVE), 256, 0, stream>>>(__VA_ARGS__)
+template <typename T, int MODE>
+static int launch_sell(int64_t nrows, int64_t nslice, const int64_t *soff, const int *col,
+                       const T *val, const int *srows, const T *x, double alpha,
+                       double beta, const T *rhs, const T *M, T *y, hipStream_t stream) {
+    sell_k<T, MODE><<<amg_nblocks(nslice * WAVE), 256, 0, stream>>>(
+        nrows, nslice, soff, col, val, srows, x, alpha, beta, rhs, M, y);
+    return (int)hipGetLastError();
+}
 
 extern "C" int amg_sell_spmv_f64(int64_t nrows, int64_t nslice, const int64_t *soff,
                                  const int *col, const double *val, const int *srows,
                                  const double *x, double alpha, double beta, double *y,
                                  hipStream_t stream) {
-    SELL_LAUNCH(double, 0, nrows, nslice, soff, col, val, srows, x, alpha, beta,
-                nullptr, nullptr, y);
-    return (int)hipGetLastError();
+    return launch_sell<double, 0>(nrows, nslice, soff, col, val, srows, x, alpha, beta,
+                                  nullptr, nullptr, y, stream);
+}
+extern "C" int amg_sell_spmv_f32(int64_t nrows, int64_t nslice, const int64_t *soff,
+                                 const int *col, const float *val, const int *srows,
+                                 const float *x, double alpha, double beta, float *y,
+                                 hipStream_t stream) {
+    return launch_sell<float, 0>(nrows, nslice, soff, col, val, srows, x, alpha, beta,
+                                 nullptr, nullptr, y, stream);
 }
 
 extern "C" int amg_sell_residual_f64(int64_t nrows, int64_t nslice, const int64_t *soff,
                                      const int *col, const double *val, const int *srows,
                                      const double *rhs, const double *x, double *r,
                                      hipStream_t stream) {
-    SELL_LAUNCH(double, 1, nrows, nslice, soff, col, val, srows, x, 0.0, 0.0, rhs,
-                nullptr, r);
-    return (int)hipGetLastError();
+    return launch_sell<double, 1>(nrows, nslice, soff, col, val, srows, x, 0.0, 0.0, rhs,
+                                  nullptr, r, stream);
+}
+extern "C" int amg_sell_residual_f32(int64_t nrows, int64_t nslice, const int64_t *soff,
+                                     const int *col, const float *val, const int *srows,
+                                     const float *rhs, const float *x, float *r,
+                                     hipStream_t stream) {
+    return launch_sell<float, 1>(nrows, nslice, soff, col, val, srows, x, 0.0, 0.0, rhs,
+                                 nullptr, r, stream);
 }
 
 extern "C" int amg_sell_relax_f64(int64_t nrows, int64_t nslice, const int64_t *soff,
                                   const int *col, const double *val, const int *srows,
                                   const double *M, const double *rhs, const double *x,
                                   double *xn, hipStream_t stream) {
-    SELL_LAUNCH(double, 2, nrows, nslice, soff, col, val, srows, x, 0.0, 0.0, rhs, M,
-                xn);
-    return (int)hipGetLastError();
+    return launch_sell<double, 2>(nrows, nslice, soff, col, val, srows, x, 0.0, 0.0, rhs,
+                                  M, xn, stream);
 }
-
-extern "C" int amg_sell_spmv_f32(int64_t nrows, int64_t nslice, const int64_t *soff,
-                                 const int *col, const float *val, const int *srows,
-                                 const float *x, double alpha, double beta, float *y,
-                                 hipStream_t stream) {
-    SELL_LAUNCH(float, 0, nrows, nslice, soff, col, val, srows, x, alpha, beta,
-                nullptr, nullptr, y);
-    return (int)hipGetLastError();
-}
-
-extern "C" int amg_sell_residual_f32(int64_t nrows, int64_t nslice, const int64_t *soff,
-                                     const int *col, const float *val, const int *srows,
-                                     const float *rhs, const float *x, float *r,
-                                     hipStream_t stream) {
-    SELL_LAUNCH(float, 1, nrows, nslice, soff, col, val, srows, x, 0.0, 0.0, rhs,
-                nullptr, r);
-    return (int)hipGetLastError();
-}
-
 extern "C" int amg_sell_relax_f32(int64_t nrows, int64_t nslice, const int64_t *soff,
                                   const int *col, const float *val, const int *srows,
                                   const float *M, const float *rhs, const float *x,
                                   float *xn, hipStream_t stream) {
-    SELL_LAUNCH(float, 2, nrows, nslice, soff, col, val, srows, x, 0.0, 0.0, rhs, M,
-                xn);
-    return (int)hipGetLastError();
+    return launch_sell<float, 2>(nrows, nslice, soff, col, val, srows, x, 0.0, 0.0, rhs,
+                                 M, xn, stream);
 }
-#undef SELL_LAUNCH
 
 // CSR -> SELL-64 fill: one wave per slice, iterating the element index i so
 // every store of a wave is fully coalesced (lane-major); the CSR reads are
@@ -291,22 +319,26 @@ __global__ void sell_fill_k(int64_t nrows, int64_t nslice, const int *__restrict
     }
 }
 
-extern "C" int amg_sell_fill_f64(int64_t nrows, int64_t nslice, const int *ptr,
-                                 const int *col, const double *val,
-                                 const int64_t *soff, const int *srows, int *scol,
-                                 double *sval, hipStream_t stream) {
-    sell_fill_k<double><<<nblocks(nslice * WAVE), 256, 0, stream>>>(
+template <typename T>
+static int launch_sell_fill(int64_t nrows, int64_t nslice, const int *ptr, const int *col,
+                            const T *val, const int64_t *soff, const int *srows,
+                            int *scol, T *sval, hipStream_t stream) {
+    sell_fill_k<T><<<amg_nblocks(nslice * WAVE), 256, 0, stream>>>(
         nrows, nslice, ptr, col, val, soff, srows, scol, sval);
     return (int)hipGetLastError();
 }
 
+extern "C" int amg_sell_fill_f64(int64_t nrows, int64_t nslice, const int *ptr,
+                                 const int *col, const double *val,
+                                 const int64_t *soff, const int *srows, int *scol,
+                                 double *sval, hipStream_t stream) {
+    return launch_sell_fill(nrows, nslice, ptr, col, val, soff, srows, scol, sval, stream);
+}
 extern "C" int amg_sell_fill_f32(int64_t nrows, int64_t nslice, const int *ptr,
                                  const int *col, const float *val,
                                  const int64_t *soff, const int *srows, int *scol,
                                  float *sval, hipStream_t stream) {
-    sell_fill_k<float><<<nblocks(nslice * WAVE), 256, 0, stream>>>(
-        nrows, nslice, ptr, col, val, soff, srows, scol, sval);
-    return (int)hipGetLastError();
+    return launch_sell_fill(nrows, nslice, ptr, col, val, soff, srows, scol, sval, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -432,27 +464,65 @@ __global__ void fill_k(int64_t n, double v, T *__restrict__ x) {
     for (; i < n; i += stride) x[i] = (T)v;
 }
 
+template <typename T>
+static int launch_axpby(int64_t n, double a, const T *x, double b, T *y,
+                        hipStream_t stream) {
+    axpby_k<T><<<amg_nblocks(n), 256, 0, stream>>>(n, a, x, b, y);
+    return (int)hipGetLastError();
+}
+
+template <typename T>
+static int launch_axpbypcz(int64_t n, double a, const T *x, double b, const T *y,
+                           double c, T *z, hipStream_t stream) {
+    axpbypcz_k<T><<<amg_nblocks(n), 256, 0, stream>>>(n, a, x, b, y, c, z);
+    return (int)hipGetLastError();
+}
+
+template <typename T>
+static int launch_vmul(int64_t n, double a, const T *m, const T *x, double b, T *z,
+                       hipStream_t stream) {
+    vmul_k<T><<<amg_nblocks(n), 256, 0, stream>>>(n, a, m, x, b, z);
+    return (int)hipGetLastError();
+}
+
+template <typename T>
+static int launch_fill(int64_t n, double v, T *x, hipStream_t stream) {
+    fill_k<T><<<amg_nblocks(n), 256, 0, stream>>>(n, v, x);
+    return (int)hipGetLastError();
+}
+
 extern "C" int amg_axpby_f64(int64_t n, double a, const double *x, double b, double *y,
                              hipStream_t stream) {
-    axpby_k<double><<<nblocks(n), 256, 0, stream>>>(n, a, x, b, y);
-    return (int)hipGetLastError();
+    return launch_axpby(n, a, x, b, y, stream);
+}
+extern "C" int amg_axpby_f32(int64_t n, double a, const float *x, double b, float *y,
+                             hipStream_t stream) {
+    return launch_axpby(n, a, x, b, y, stream);
 }
 
 extern "C" int amg_axpbypcz_f64(int64_t n, double a, const double *x, double b,
                                 const double *y, double c, double *z, hipStream_t stream) {
-    axpbypcz_k<double><<<nblocks(n), 256, 0, stream>>>(n, a, x, b, y, c, z);
-    return (int)hipGetLastError();
+    return launch_axpbypcz(n, a, x, b, y, c, z, stream);
+}
+extern "C" int amg_axpbypcz_f32(int64_t n, double a, const float *x, double b,
+                                const float *y, double c, float *z, hipStream_t stream) {
+    return launch_axpbypcz(n, a, x, b, y, c, z, stream);
 }
 
 extern "C" int amg_vmul_f64(int64_t n, double a, const double *m, const double *x,
                             double b, double *z, hipStream_t stream) {
-    vmul_k<double><<<nblocks(n), 256, 0, stream>>>(n, a, m, x, b, z);
-    return (int)hipGetLastError();
+    return launch_vmul(n, a, m, x, b, z, stream);
+}
+extern "C" int amg_vmul_f32(int64_t n, double a, const float *m, const float *x, double b,
+                            float *z, hipStream_t stream) {
+    return launch_vmul(n, a, m, x, b, z, stream);
 }
 
 extern "C" int amg_fill_f64(int64_t n, double v, double *x, hipStream_t stream) {
-    fill_k<double><<<nblocks(n), 256, 0, stream>>>(n, v, x);
-    return (int)hipGetLastError();
+    return launch_fill(n, v, x, stream);
+}
+extern "C" int amg_fill_f32(int64_t n, double v, float *x, hipStream_t stream) {
+    return launch_fill(n, v, x, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -508,18 +578,27 @@ __global__ void dot2_k(int64_t n, const T *__restrict__ x1, const T *__restrict_
     }
 }
 
+template <typename T>
+static int launch_dot(int64_t n, const T *x, const T *y, double *out, hipStream_t stream) {
+    fill_k<double><<<1, 64, 0, stream>>>(1, 0.0, out);
+    dot_k<T><<<amg_nblocks(n, 256, 2048), 256, 0, stream>>>(n, x, y, out);
+    return (int)hipGetLastError();
+}
+
 extern "C" int amg_dot_f64(int64_t n, const double *x, const double *y, double *out,
                            hipStream_t stream) {
-    fill_k<double><<<1, 64, 0, stream>>>(1, 0.0, out);
-    dot_k<double><<<nblocks(n, 256, 2048), 256, 0, stream>>>(n, x, y, out);
-    return (int)hipGetLastError();
+    return launch_dot(n, x, y, out, stream);
+}
+extern "C" int amg_dot_f32(int64_t n, const float *x, const float *y, double *out,
+                           hipStream_t stream) {
+    return launch_dot(n, x, y, out, stream);
 }
 
 extern "C" int amg_dot2_f64(int64_t n, const double *x1, const double *y1,
                             const double *x2, const double *y2, double *out,
                             hipStream_t stream) {
     fill_k<double><<<1, 64, 0, stream>>>(2, 0.0, out);
-    dot2_k<double><<<nblocks(n, 256, 2048), 256, 0, stream>>>(n, x1, y1, x2, y2, out);
+    dot2_k<double><<<amg_nblocks(n, 256, 2048), 256, 0, stream>>>(n, x1, y1, x2, y2, out);
     return (int)hipGetLastError();
 }
 
@@ -543,16 +622,36 @@ __global__ void scatter_k(int64_t n, const T *__restrict__ buf,
     for (; i < n; i += stride) x[idx[i]] = buf[i];
 }
 
+template <typename T>
+static int launch_gather(int64_t n, const T *x, const int *idx, T *buf,
+                         hipStream_t stream) {
+    gather_k<T><<<amg_nblocks(n), 256, 0, stream>>>(n, x, idx, buf);
+    return (int)hipGetLastError();
+}
+
+template <typename T>
+static int launch_scatter(int64_t n, const T *buf, const int *idx, T *x,
+                          hipStream_t stream) {
+    scatter_k<T><<<amg_nblocks(n), 256, 0, stream>>>(n, buf, idx, x);
+    return (int)hipGetLastError();
+}
+
 extern "C" int amg_gather_f64(int64_t n, const double *x, const int *idx, double *buf,
                               hipStream_t stream) {
-    gather_k<double><<<nblocks(n), 256, 0, stream>>>(n, x, idx, buf);
-    return (int)hipGetLastError();
+    return launch_gather(n, x, idx, buf, stream);
+}
+extern "C" int amg_gather_f32(int64_t n, const float *x, const int *idx, float *buf,
+                              hipStream_t stream) {
+    return launch_gather(n, x, idx, buf, stream);
 }
 
 extern "C" int amg_scatter_f64(int64_t n, const double *buf, const int *idx, double *x,
                                hipStream_t stream) {
-    scatter_k<double><<<nblocks(n), 256, 0, stream>>>(n, buf, idx, x);
-    return (int)hipGetLastError();
+    return launch_scatter(n, buf, idx, x, stream);
+}
+extern "C" int amg_scatter_f32(int64_t n, const float *buf, const int *idx, float *x,
+                               hipStream_t stream) {
+    return launch_scatter(n, buf, idx, x, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -576,115 +675,19 @@ __global__ void gemv_k(int n, const T *__restrict__ a, const T *__restrict__ f,
     }
 }
 
+template <typename T>
+static int launch_gemv(int64_t n, const T *a, const T *f, T *u, hipStream_t stream) {
+    gemv_k<T><<<amg_nblocks(n * WAVE), 256, 0, stream>>>((int)n, a, f, u);
+    return (int)hipGetLastError();
+}
+
 extern "C" int amg_gemv_f64(int64_t n, const double *a, const double *f, double *u,
                             hipStream_t stream) {
-    gemv_k<double><<<nblocks(n * WAVE), 256, 0, stream>>>((int)n, a, f, u);
-    return (int)hipGetLastError();
-}
-
-
-// ---------------------------------------------------------------------------
-// fp32 entry points (mixed-precision AMG: fp32 hierarchy under a fp64 Krylov
-// loop — SURVEY §5.9, reference examples/mixed_precision.cpp). Reductions
-// accumulate in fp64 regardless of storage type.
-// ---------------------------------------------------------------------------
-extern "C" int amg_spmv_f32(int64_t nrows, int64_t nnz, const int *ptr, const int *col,
-                            const float *val, const float *x, double alpha, double beta,
-                            float *y, int subw, hipStream_t stream) {
-    if (subw <= 0) subw = amg_pick_subw(nrows, nnz);
-    int grid = nblocks(nrows * subw);
-#define CASE(SW)                                                                        \
-    case SW:                                                                            \
-        if (beta == 0.0)                                                                \
-            spmv_k<float, SW, true><<<grid, 256, 0, stream>>>(nrows, ptr, col, val, x,  \
-                                                              alpha, beta, y);          \
-        else                                                                            \
-            spmv_k<float, SW, false><<<grid, 256, 0, stream>>>(nrows, ptr, col, val, x, \
-                                                               alpha, beta, y);         \
-        break;
-    switch (subw) {
-        CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef CASE
-    return (int)hipGetLastError();
-}
-
-extern "C" int amg_residual_f32(int64_t nrows, int64_t nnz, const int *ptr, const int *col,
-                                const float *val, const float *rhs, const float *x,
-                                float *r, int subw, hipStream_t stream) {
-    if (subw <= 0) subw = amg_pick_subw(nrows, nnz);
-    int grid = nblocks(nrows * subw);
-#define CASE(SW)                                                                      \
-    case SW:                                                                          \
-        residual_k<float, SW><<<grid, 256, 0, stream>>>(nrows, ptr, col, val, rhs, x, r); \
-        break;
-    switch (subw) {
-        CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef CASE
-    return (int)hipGetLastError();
-}
-
-extern "C" int amg_relax_diag_f32(int64_t nrows, int64_t nnz, const int *ptr,
-                                  const int *col, const float *val, const float *M,
-                                  const float *rhs, const float *x, float *t, int subw,
-                                  hipStream_t stream) {
-    if (subw <= 0) subw = amg_pick_subw(nrows, nnz);
-    int grid = nblocks(nrows * subw);
-#define CASE(SW)                                                                          \
-    case SW:                                                                              \
-        relax_diag_k<float, SW><<<grid, 256, 0, stream>>>(nrows, ptr, col, val, M, rhs,   \
-                                                          x, t);                         \
-        break;
-    switch (subw) {
-        CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef CASE
-    return (int)hipGetLastError();
-}
-
-extern "C" int amg_axpby_f32(int64_t n, double a, const float *x, double b, float *y,
-                             hipStream_t stream) {
-    axpby_k<float><<<nblocks(n), 256, 0, stream>>>(n, a, x, b, y);
-    return (int)hipGetLastError();
-}
-extern "C" int amg_axpbypcz_f32(int64_t n, double a, const float *x, double b,
-                                const float *y, double c, float *z, hipStream_t stream) {
-    axpbypcz_k<float><<<nblocks(n), 256, 0, stream>>>(n, a, x, b, y, c, z);
-    return (int)hipGetLastError();
-}
-extern "C" int amg_vmul_f32(int64_t n, double a, const float *m, const float *x, double b,
-                            float *z, hipStream_t stream) {
-    vmul_k<float><<<nblocks(n), 256, 0, stream>>>(n, a, m, x, b, z);
-    return (int)hipGetLastError();
-}
-extern "C" int amg_fill_f32(int64_t n, double v, float *x, hipStream_t stream) {
-    fill_k<float><<<nblocks(n), 256, 0, stream>>>(n, v, x);
-    return (int)hipGetLastError();
-}
-extern "C" int amg_dot_f32(int64_t n, const float *x, const float *y, double *out,
-                           hipStream_t stream) {
-    fill_k<double><<<1, 64, 0, stream>>>(1, 0.0, out);
-    dot_k<float><<<nblocks(n, 256, 2048), 256, 0, stream>>>(n, x, y, out);
-    return (int)hipGetLastError();
-}
-extern "C" int amg_gather_f32(int64_t n, const float *x, const int *idx, float *buf,
-                              hipStream_t stream) {
-    gather_k<float><<<nblocks(n), 256, 0, stream>>>(n, x, idx, buf);
-    return (int)hipGetLastError();
-}
-extern "C" int amg_scatter_f32(int64_t n, const float *buf, const int *idx, float *x,
-                               hipStream_t stream) {
-    scatter_k<float><<<nblocks(n), 256, 0, stream>>>(n, buf, idx, x);
-    return (int)hipGetLastError();
+    return launch_gemv(n, a, f, u, stream);
 }
 extern "C" int amg_gemv_f32(int64_t n, const float *a, const float *f, float *u,
                             hipStream_t stream) {
-    gemv_k<float><<<nblocks(n * WAVE), 256, 0, stream>>>((int)n, a, f, u);
-    return (int)hipGetLastError();
+    return launch_gemv(n, a, f, u, stream);
 }
 
 // precision casts (mixed-precision boundary)
@@ -699,11 +702,11 @@ __global__ void cast_s2d_k(int64_t n, const float *__restrict__ src, double *__r
     for (; i < n; i += stride) dst[i] = (double)src[i];
 }
 extern "C" int amg_cast_d2s(int64_t n, const double *src, float *dst, hipStream_t s) {
-    cast_d2s_k<<<nblocks(n), 256, 0, s>>>(n, src, dst);
+    cast_d2s_k<<<amg_nblocks(n), 256, 0, s>>>(n, src, dst);
     return (int)hipGetLastError();
 }
 extern "C" int amg_cast_s2d(int64_t n, const float *src, double *dst, hipStream_t s) {
-    cast_s2d_k<<<nblocks(n), 256, 0, s>>>(n, src, dst);
+    cast_s2d_k<<<amg_nblocks(n), 256, 0, s>>>(n, src, dst);
     return (int)hipGetLastError();
 }
 
@@ -735,7 +738,7 @@ __global__ void gs_color_k(int64_t nlist, const int *__restrict__ rows,
 extern "C" int amg_gs_color_f64(int64_t nlist, const int *rows, const int *ptr,
                                 const int *col, const double *val, const double *b,
                                 double *x, hipStream_t stream) {
-    gs_color_k<<<nblocks(nlist), 256, 0, stream>>>(nlist, rows, ptr, col, val, b, x);
+    gs_color_k<<<amg_nblocks(nlist), 256, 0, stream>>>(nlist, rows, ptr, col, val, b, x);
     return (int)hipGetLastError();
 }
 
@@ -768,7 +771,7 @@ __global__ void cg_tail_k(int64_t n, double alpha, const double *__restrict__ p,
 extern "C" int amg_cg_tail_f64(int64_t n, double alpha, const double *p, const double *q,
                                double *x, double *r, double *out, hipStream_t stream) {
     fill_k<double><<<1, 64, 0, stream>>>(1, 0.0, out);
-    cg_tail_k<<<nblocks(n, 256, 2048), 256, 0, stream>>>(n, alpha, p, q, x, r, out);
+    cg_tail_k<<<amg_nblocks(n, 256, 2048), 256, 0, stream>>>(n, alpha, p, q, x, r, out);
     return (int)hipGetLastError();
 }
 
@@ -827,49 +830,38 @@ __global__ void cspmv_k(int64_t nrows, const int *__restrict__ ptr,
     }
 }
 
-#define CSPMV_LAUNCH(SW, MODE)                                                     \
-    cspmv_k<SW, MODE><<<nblocks(nrows * SW), 256, 0, stream>>>(                    \
-        nrows, ptr, col, (const c128 *)val, (const c128 *)x, a, b,                 \
-        (const c128 *)rhs, (const c128 *)M, (c128 *)y)
-
+template <int MODE>
 static int cspmv_dispatch(int64_t nrows, int64_t nnz, const int *ptr, const int *col,
                           const void *val, const void *x, c128 a, c128 b,
-                          const void *rhs, const void *M, void *y, int subw, int mode,
+                          const void *rhs, const void *M, void *y, int subw,
                           hipStream_t stream) {
-    if (subw <= 0) subw = amg_pick_subw(nrows, nnz);
-#define CC(SW)                                                                      \
-    case SW:                                                                        \
-        if (mode == 0) CSPMV_LAUNCH(SW, 0);                                         \
-        else if (mode == 1) CSPMV_LAUNCH(SW, 1);                                    \
-        else CSPMV_LAUNCH(SW, 2);                                                   \
-        break;
-    switch (subw) {
-        CC(1) CC(2) CC(4) CC(8) CC(16) CC(32) CC(64)
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef CC
-    return (int)hipGetLastError();
+    return by_subw(subw, nrows, nnz, [&](auto sw) {
+        constexpr int SW = decltype(sw)::value;
+        cspmv_k<SW, MODE><<<amg_nblocks(nrows * SW), 256, 0, stream>>>(
+            nrows, ptr, col, (const c128 *)val, (const c128 *)x, a, b, (const c128 *)rhs,
+            (const c128 *)M, (c128 *)y);
+    });
 }
 
 extern "C" int amg_spmv_c128(int64_t nrows, int64_t nnz, const int *ptr, const int *col,
                              const void *val, const void *x, double ar, double ai,
                              double br, double bi, void *y, int subw,
                              hipStream_t stream) {
-    return cspmv_dispatch(nrows, nnz, ptr, col, val, x, {ar, ai}, {br, bi}, nullptr,
-                          nullptr, y, subw, 0, stream);
+    return cspmv_dispatch<0>(nrows, nnz, ptr, col, val, x, {ar, ai}, {br, bi}, nullptr,
+                             nullptr, y, subw, stream);
 }
 extern "C" int amg_residual_c128(int64_t nrows, int64_t nnz, const int *ptr,
                                  const int *col, const void *val, const void *rhs,
                                  const void *x, void *r, int subw, hipStream_t stream) {
-    return cspmv_dispatch(nrows, nnz, ptr, col, val, x, {0, 0}, {0, 0}, rhs, nullptr,
-                          r, subw, 1, stream);
+    return cspmv_dispatch<1>(nrows, nnz, ptr, col, val, x, {0, 0}, {0, 0}, rhs, nullptr,
+                             r, subw, stream);
 }
 extern "C" int amg_relax_diag_c128(int64_t nrows, int64_t nnz, const int *ptr,
                                    const int *col, const void *val, const void *M,
                                    const void *rhs, const void *x, void *t, int subw,
                                    hipStream_t stream) {
-    return cspmv_dispatch(nrows, nnz, ptr, col, val, x, {0, 0}, {0, 0}, rhs, M, t,
-                          subw, 2, stream);
+    return cspmv_dispatch<2>(nrows, nnz, ptr, col, val, x, {0, 0}, {0, 0}, rhs, M, t,
+                             subw, stream);
 }
 
 template <int MODE>  // 0: y=ax+by  1: z=ax+by+cz  2: z=a(m.x)+bz
@@ -897,14 +889,14 @@ __global__ void cvec_k(int64_t n, c128 a, const c128 *__restrict__ x, c128 b,
 
 extern "C" int amg_axpby_c128(int64_t n, double ar, double ai, const void *x,
                               double br, double bi, void *y, hipStream_t stream) {
-    cvec_k<0><<<nblocks(n), 256, 0, stream>>>(n, {ar, ai}, (const c128 *)x, {br, bi},
+    cvec_k<0><<<amg_nblocks(n), 256, 0, stream>>>(n, {ar, ai}, (const c128 *)x, {br, bi},
                                               nullptr, {0, 0}, nullptr, (c128 *)y);
     return (int)hipGetLastError();
 }
 extern "C" int amg_axpbypcz_c128(int64_t n, double ar, double ai, const void *x,
                                  double br, double bi, const void *y, double cr,
                                  double ci, void *z, hipStream_t stream) {
-    cvec_k<1><<<nblocks(n), 256, 0, stream>>>(n, {ar, ai}, (const c128 *)x, {br, bi},
+    cvec_k<1><<<amg_nblocks(n), 256, 0, stream>>>(n, {ar, ai}, (const c128 *)x, {br, bi},
                                               (const c128 *)y, {cr, ci}, nullptr,
                                               (c128 *)z);
     return (int)hipGetLastError();
@@ -912,7 +904,7 @@ extern "C" int amg_axpbypcz_c128(int64_t n, double ar, double ai, const void *x,
 extern "C" int amg_vmul_c128(int64_t n, double ar, double ai, const void *m,
                              const void *x, double br, double bi, void *z,
                              hipStream_t stream) {
-    cvec_k<2><<<nblocks(n), 256, 0, stream>>>(n, {ar, ai}, (const c128 *)x, {br, bi},
+    cvec_k<2><<<amg_nblocks(n), 256, 0, stream>>>(n, {ar, ai}, (const c128 *)x, {br, bi},
                                               nullptr, {0, 0}, (const c128 *)m,
                                               (c128 *)z);
     return (int)hipGetLastError();
@@ -938,7 +930,7 @@ __global__ void cdot_k(int64_t n, const c128 *__restrict__ x,
 
 extern "C" int amg_dot_c128(int64_t n, const void *x, const void *y, double *out,
                             hipStream_t stream) {
-    cdot_k<<<nblocks(n, 256, 2048), 256, 0, stream>>>(n, (const c128 *)x,
+    cdot_k<<<amg_nblocks(n, 256, 2048), 256, 0, stream>>>(n, (const c128 *)x,
                                                       (const c128 *)y, out);
     return (int)hipGetLastError();
 }
@@ -964,7 +956,7 @@ __global__ void cgemv_k(int64_t n, const c128 *__restrict__ inv,
 
 extern "C" int amg_gemv_c128(int64_t n, const void *inv, const void *f, void *y,
                              hipStream_t stream) {
-    cgemv_k<<<nblocks(n * WAVE), 256, 0, stream>>>(n, (const c128 *)inv,
+    cgemv_k<<<amg_nblocks(n * WAVE), 256, 0, stream>>>(n, (const c128 *)inv,
                                                    (const c128 *)f, (c128 *)y);
     return (int)hipGetLastError();
 }
@@ -977,6 +969,6 @@ __global__ void cfill_k(int64_t n, c128 v, c128 *__restrict__ x) {
 
 extern "C" int amg_fill_c128(int64_t n, double vr, double vi, void *x,
                              hipStream_t stream) {
-    cfill_k<<<nblocks(n), 256, 0, stream>>>(n, {vr, vi}, (c128 *)x);
+    cfill_k<<<amg_nblocks(n), 256, 0, stream>>>(n, {vr, vi}, (c128 *)x);
     return (int)hipGetLastError();
 }
