@@ -126,6 +126,16 @@ for _op in ("spmv", "residual", "relax_diag", "axpby", "axpbypcz", "vmul", "fill
             "sell_fill"):
     _SIGS[f"amg_{_op}_f32"] = _SIGS[f"amg_{_op}_f64"]
 
+# SPAI-1 device setup (setup.hip).  Kept beside _SIGS, whose entry count
+# tests/test_launch_dispatch.py pins; lib() binds both tables alike.
+_SPAI1_SIGS = {
+    "amg_spai1_short_max": [],
+    # n, ptr, col, val, mval, flag, nlong, longrows, kmax, slots, work, stream
+    "amg_setup_spai1": [ctypes.c_int64] + [ctypes.c_void_p] * 5
+                       + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                          ctypes.c_void_p, ctypes.c_void_p],
+}
+
 
 def lib():
     global _LIB
@@ -143,7 +153,7 @@ def lib():
                 "--inplace` — GPU ops do not fall back to eager torch"
             )
         _LIB = ctypes.CDLL(path)
-        for name, argtypes in _SIGS.items():
+        for name, argtypes in {**_SIGS, **_SPAI1_SIGS}.items():
             fn = getattr(_LIB, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

@@ -80,6 +80,48 @@ def spai0(A):
     return m
 
 
+# Byte budget of the SPAI-1 long-row workspace (one kmax x kmax Gram matrix
+# per row in flight).  A design constant, not a measured one: nobody has yet
+# timed the long tier against the number of slots this buys.
+SPAI1_WORK_BYTES = 256 << 20
+SPAI1_MAX_SLOTS = 1024  # blocks of the long tier; four per CU fill the device
+
+
+def spai1(A):
+    """SPAI-1 approximate inverse of the device matrix A, built on the device
+    (amg_setup_spai1, csrc/hip/setup.hip): a DeviceCSR that shares A.ptr and
+    A.col and owns its values.  Rows of A must have sorted columns.  Raises
+    OverflowError if one row's Gram matrix alone exceeds SPAI1_WORK_BYTES
+    (callers fall back to the host routine) and RuntimeError if a row's local
+    least-squares system is singular."""
+    t = _torch()
+    dev = A.val.device
+    if A.nrows != A.ncols:
+        raise ValueError("spai1 needs a square matrix")
+    lens = A.ptr[1:] - A.ptr[:-1]
+    longrows = t.nonzero(lens > lib().amg_spai1_short_max()).flatten().to(t.int32)
+    nlong = longrows.numel()
+    kmax = slots = 0
+    work = None
+    if nlong:
+        kmax = int(lens.max().item())
+        per_slot = 8 * kmax * (kmax + 2)
+        slots = min(nlong, SPAI1_MAX_SLOTS, SPAI1_WORK_BYTES // per_slot)
+        if slots < 1:
+            raise OverflowError("spai1 row exceeds the device workspace; use host setup")
+        work = t.empty(slots * kmax * (kmax + 2), dtype=t.float64, device=dev)
+    mval = t.empty(A.nnz, dtype=t.float64, device=dev)
+    flag = t.empty(1, dtype=t.int32, device=dev)
+    check(lib().amg_setup_spai1(A.nrows, A.ptr.data_ptr(), A.col.data_ptr(),
+                                A.val.data_ptr(), mval.data_ptr(), flag.data_ptr(),
+                                nlong, longrows.data_ptr() if nlong else 0, kmax, slots,
+                                work.data_ptr() if nlong else 0, _stream()), "spai1")
+    bad = int(flag.item())
+    if bad:
+        raise RuntimeError(f"spai1: singular local system at row {bad - 1}")
+    return device_csr(A.nrows, A.ncols, A.ptr, A.col, mval)
+
+
 def gershgorin(A, scale=False):
     """Gershgorin spectral-radius bound on the device."""
     t = _torch()

@@ -3,8 +3,9 @@
 Hands the whole AMG-preconditioned CG/BiCGStab solve to the C++ driver
 (csrc/hip/driver.hip) — one ctypes call per solve, no Python in the hot
 path. Engaged automatically by make_solver for HIP-backend AMG with diagonal
-smoothers (SPAI0/damped Jacobi), dense-inverse coarse solve, and cg/bicgstab;
-anything else uses the generic Python orchestration.
+smoothers (SPAI0/damped Jacobi), Chebyshev, ILU0 with the iterated-Jacobi
+solve or SPAI-1, dense-inverse coarse solve (or the smoother on the coarsest
+level), and cg/bicgstab; anything else uses the generic Python orchestration.
 """
 import ctypes
 
@@ -46,6 +47,7 @@ class LevelDescC(ctypes.Structure):
         ("bptr", ctypes.c_void_p),
         ("bcol", ctypes.c_void_p),
         ("bval", ctypes.c_void_p),
+        ("spai1", OpDescC),
         ("ilu_iters", ctypes.c_int),
         ("ilu_damping", ctypes.c_double),
         ("ilu_jdamping", ctypes.c_double),
@@ -151,7 +153,7 @@ class NativeDriver:
 
         from ..relaxation.chebyshev import Chebyshev
         from ..relaxation.ilu0 import ILU0
-        from ..relaxation.spai0 import DiagonalSmootherBase
+        from ..relaxation.spai0 import DiagonalSmootherBase, Spai1
         from .hip import DeviceBSR, DeviceCSR, DeviceDenseSolver
 
         self.backend = backend
@@ -166,7 +168,7 @@ class NativeDriver:
             raise TypeError("native driver needs device-resident levels")
         self._mixed = bool(getattr(amg, "_mixed", False))
         def relax_ok(r):
-            if isinstance(r, (DiagonalSmootherBase, Chebyshev)):
+            if isinstance(r, (DiagonalSmootherBase, Chebyshev, Spai1)):
                 return True
             # ILU0 with the iterated-Jacobi solve (graph-capturable); the
             # exact cooperative sptrsv stays on the generic path
@@ -176,7 +178,7 @@ class NativeDriver:
         for l in levels[:-1]:
             if not relax_ok(l.relax):
                 raise TypeError(
-                    "native driver supports diagonal/Chebyshev/ILU0(jacobi)")
+                    "native driver supports diagonal/Chebyshev/ILU0(jacobi)/SPAI-1")
         if amg.coarse_solve is not None and not isinstance(
             amg.coarse_solve, DeviceDenseSolver
         ):
@@ -226,6 +228,8 @@ class NativeDriver:
                 d.M = _ptr(relax.Dinv)  # optional D^-1 scaling (may be null)
                 if relax.Dinv is not None:
                     keep.append(relax.Dinv)
+            elif isinstance(relax, Spai1):
+                _op(d.spai1, relax.M, keep)
             elif relax is not None:
                 d.M = _ptr(relax.M)
                 keep.append(relax.M)

@@ -77,11 +77,14 @@ struct OpDesc {
 // Python (backend/native.py, torch tensors) or from the torch-free GPU C API
 // (capi_gpu.hip, raw device buffers).  backend/native.py keeps a ctypes twin
 // and checks it against amg_desc_layout (driver.hip) when it binds.
+// The smoother of a level is whichever of ilu_iters, cheb_degree and
+// spai1.nrows is nonzero, else the diagonal one in M; a zeroed descriptor
+// (what capi_gpu.hip starts from) selects none of the three.
 struct LevelDesc {
     OpDesc A;  // A.nrows is the level size (CSR arrays unused when bsize > 0)
     OpDesc P;  // nrows x next->nrows
     OpDesc R;  // next->nrows x nrows
-    const double *M;  // diagonal smoother weights
+    const double *M;  // diagonal smoother weights (SPAI-0, damped Jacobi)
     double *f;
     double *u;
     double *t;  // workspace (f/u unused at level 0)
@@ -98,6 +101,10 @@ struct LevelDesc {
     const int *bptr;
     const int *bcol;
     const double *bval;
+    // SPAI-1 smoothing (spai1.nrows > 0 replaces the diagonal smoother; a
+    // zeroed descriptor means "not SPAI-1"): the approximate inverse, CSR
+    // with A's pattern, applied as x += spai1 (f - A x).  fp64 only.
+    OpDesc spai1;
     // ILU(0) smoothing via damped-Jacobi iterated triangular solves
     // (ilu_iters > 0; the reference's GPU-native ilu_solve.hpp route).
     // ilu_L strictly lower (unit diag implied), ilu_U strictly upper;

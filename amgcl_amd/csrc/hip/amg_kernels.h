@@ -91,6 +91,10 @@ int amg_setup_strong(int64_t n, const int *ptr, const int *col, const double *va
                      const double *d, double eps2, uint8_t *S, hipStream_t s);
 int amg_setup_spai0(int64_t n, const int *ptr, const int *col, const double *val,
                     double *m, hipStream_t s);
+int amg_spai1_short_max(void);
+int amg_setup_spai1(int64_t n, const int *ptr, const int *col, const double *val,
+                    double *mval, int *flag, int64_t nlong, const int *longrows, int kmax,
+                    int slots, double *work, hipStream_t s);
 int amg_scan_i32(int *a, int64_t n, hipStream_t s);
 int amg_agg_init(int64_t n, const int *ptr, const uint8_t *S, int *id, hipStream_t s);
 int amg_agg_run(int64_t n, const int *ptr, const int *col, const uint8_t *S, int *id,

@@ -4,8 +4,8 @@
 // loop) in C++: one ctypes call per solve, no Python between kernels.
 // This is the runtime counterpart of the reference's compiled solve templates
 // (amgcl/amg.hpp:514-553 cycle; amgcl/solver/cg.hpp:152-204;
-// amgcl/solver/bicgstab.hpp:176-240), specialized for the HIP backend and
-// diagonal (SPAI0 / damped-Jacobi) smoothers.
+// amgcl/solver/bicgstab.hpp:176-240), specialized for the HIP backend with
+// diagonal (SPAI0 / damped-Jacobi), Chebyshev, ILU(0) and SPAI-1 smoothers.
 //
 // Per-level relaxation uses a pointer-swapping fused kernel
 //   x_new = x + M ∘ (rhs - A x)
@@ -214,8 +214,29 @@ int ilu_apply<double>(Driver *D, const LevelDesc &L, const double *rhs, double *
     return 0;
 }
 
+// SPAI-1 smoothing step, in place on x (driver twin of relaxation/spai0.py
+// Spai1._step; parity: amgcl/relaxation/spai1.hpp:126-134):
+//   t = rhs - A x;  x += M t,  M = L.spai1.   fp64 only (SPAI-1 + mixed is
+// not offered).  From a zero guess (t null) it is x = M rhs, one kernel.
+template <typename T>
+static int spai1_apply(Driver *D, const LevelDesc &L, const T *rhs, T *x, T *t) {
+    return (int)hipErrorInvalidValue;  // specialized for double below
+}
+
+template <>
+int spai1_apply<double>(Driver *D, const LevelDesc &L, const double *rhs, double *x,
+                        double *t) {
+    if (!t) return op_spmv<double>(D, L.spai1, rhs, 1.0, 0.0, x);
+    CHK(level_residual<double>(D, L, rhs, x, t));
+    return op_spmv<double>(D, L.spai1, t, 1.0, 1.0, x);
+}
+
 template <typename T>
 static int relax_swap(Driver *D, const LevelDesc &L, const T *rhs, T **x, T **xn) {
+    if (L.spai1.nrows > 0) {  // in place, no pointer swap
+        CHK(spai1_apply<T>(D, L, rhs, *x, *xn));
+        return 0;
+    }
     if (L.ilu_iters) {  // in place, no pointer swap
         CHK(ilu_apply<T>(D, L, rhs, *x, *xn));
         return 0;
@@ -269,6 +290,8 @@ static int cycle(Driver *D, int li, const T *f, T **u_io, T **scratch, bool u_is
     // relax_zero writes into the swap buffer and swaps, so zero-guess and
     // general smooths have identical pointer parity (no copy-back needed)
     auto relax_zero = [&](LevelDesc &LL, const T *ff, T **u2, T **sc) -> int {
+        // in place like its general form, so neither swaps
+        if (LL.spai1.nrows > 0) return spai1_apply<T>(D, LL, ff, *u2, (T *)nullptr);
         if (LL.cheb_degree || LL.bsize || LL.ilu_iters) {
             // no fused zero-guess form for these smoothers: clear + general
             CHK(fill<T>(LL.A.nrows, 0.0, *u2, D->stream));
@@ -410,7 +433,7 @@ extern "C" void *amg_driver_create(const LevelDesc *levels, int nlevels,
     };
     settle(D->a64);
     for (LevelDesc &L : D->lv)
-        for (OpDesc *op : {&L.A, &L.P, &L.R, &L.ilu_L, &L.ilu_U}) settle(*op);
+        for (OpDesc *op : {&L.A, &L.P, &L.R, &L.spai1, &L.ilu_L, &L.ilu_U}) settle(*op);
     D->coarse_inv = coarse_inv;
     D->ncoarse = ncoarse;
     D->npre = npre;
@@ -476,7 +499,7 @@ extern "C" int amg_desc_layout(int64_t *out, int cap) {
         OP(sval), OP(srows),
         LV(A), LV(P), LV(R), LV(M), LV(f), LV(u), LV(t), LV(cheb_degree), LV(cheb_theta),
         LV(cheb_delta), LV(cheb_sigma1), LV(cheb_d), LV(bsize), LV(nbrows), LV(bptr), LV(bcol),
-        LV(bval), LV(ilu_iters), LV(ilu_damping), LV(ilu_jdamping), LV(ilu_L), LV(ilu_U),
+        LV(bval), LV(spai1), LV(ilu_iters), LV(ilu_damping), LV(ilu_jdamping), LV(ilu_L), LV(ilu_U),
         LV(ilu_dinv), LV(ilu_y), LV(ilu_s), LV(ilu_b)};
 #undef OP
 #undef LV

@@ -14,6 +14,7 @@
 //   - SpGEMM with per-wave LDS hash accumulators (Galerkin triple product,
 //     coarsening/detail/galerkin.hpp:42)
 //   - SPAI-0 / damped-Jacobi smoother weights on device
+//   - SPAI-1 approximate inverse (per-row normal equations + Cholesky)
 //   - inclusive i32 scan
 //
 // All kernels are deterministic except SpGEMM value accumulation order
@@ -189,6 +190,260 @@ extern "C" int amg_gershgorin(int64_t n, const int *ptr, const int *col, const d
                               int scale, double *out, hipStream_t s) {
     hipMemsetAsync(out, 0, sizeof(double), s);
     gersh_k<<<nblk(n, 256, 1024), 256, 0, s>>>(n, ptr, col, val, scale, out);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// SPAI-1 smoother setup (amgcl/relaxation/spai1.hpp:82-120)
+// ---------------------------------------------------------------------------
+// M has A's pattern, so only its values are produced.  With I = {c_0 < ... <
+// c_{k-1}} the pattern of row i, row i of M minimises ||e_i^T - m^T A(I,:)||
+// over the ROWS of A in I (the reference's QR problem).  Its normal equations
+//   G m = rhs,   G[a][b] = <A(c_a,:), A(c_b,:)>,   rhs[a] = A(c_a, i)
+// need only CSR rows of A (no transpose) and are solved by Cholesky.  Rows of
+// A must have sorted columns: the sparse dots are two-pointer merges and rhs
+// is a binary search.
+//
+// Two tiers by row length k: up to SPAI1_SHORT one wave per row with G in
+// LDS; longer rows come through a worklist, one block per row with G in a
+// global workspace slot.
+//
+// A pivot <= k * 2^-52 * G[c][c] (G's original diagonal entry) cannot be told
+// from zero, since that is the bound on the rounding error of the computed
+// pivot; such a row reports row+1 through atomicMax on *flag and its output
+// is unspecified.
+//
+// The pivot test is only as sharp as sqrt and division are.  The library is
+// built with -ffast-math, under which gfx950's f64 division is a Newton-
+// refined reciprocal with one residual correction and f64 sqrt keeps its full
+// refinement: both stay within an ulp, which the bound above allows for.
+
+#define SPAI1_SHORT 32                // longest row of the wave-per-row tier
+#define SPAI1_LD (SPAI1_SHORT + 1)    // LDS leading dimension, padded: lanes a
+                                      // reading G[a][j] fall on banks 2(a+j) % 64
+#define SPAI1_WPB 4                   // waves (rows in flight) per block
+#define SPAI1_EPS 2.220446049250313e-16  // 2^-52
+
+// Orders one wave's LDS traffic: the LDS serves a wave's accesses in issue
+// order, so what is left to prevent is the compiler moving them.
+__device__ __forceinline__ void spai1_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// <A(r,:), A(s,:)> for the rows stored at [i, ie) and [j, je)
+__device__ __forceinline__ double spai1_row_dot(const int *__restrict__ col,
+                                                const double *__restrict__ val, int i,
+                                                int ie, int j, int je) {
+    double s = 0.0;
+    if (i == j) {
+        for (; i < ie; ++i) s += val[i] * val[i];
+        return s;
+    }
+    while (i < ie && j < je) {
+        int ci = col[i], cj = col[j];
+        if (ci == cj) s += val[i] * val[j];
+        i += (ci <= cj);
+        j += (cj <= ci);
+    }
+    return s;
+}
+
+// A(r, c) for the row stored at [lo, hi), 0 if absent
+__device__ __forceinline__ double spai1_entry(const int *__restrict__ col,
+                                              const double *__restrict__ val, int lo,
+                                              int hi, int c) {
+    const int end = hi;
+    while (lo < hi) {
+        int mid = lo + ((hi - lo) >> 1);
+        if (col[mid] < c) lo = mid + 1; else hi = mid;
+    }
+    return (lo < end && col[lo] == c) ? val[lo] : 0.0;
+}
+
+// p in [0, k(k+1)/2) -> (a <= b) with p = b(b+1)/2 + a
+__device__ __forceinline__ void spai1_pair(int64_t p, int *a, int *b) {
+    int64_t t = (int64_t)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);
+    while (t * (t + 1) / 2 > p) --t;
+    while ((t + 1) * (t + 2) / 2 <= p) ++t;
+    *b = (int)t;
+    *a = (int)(p - t * (t + 1) / 2);
+}
+
+// Short tier: rows with 1 <= k <= SPAI1_SHORT, one wave per row.
+__global__ __launch_bounds__(64 * SPAI1_WPB) void spai1_short_k(
+    int64_t n, const int *__restrict__ ptr, const int *__restrict__ col,
+    const double *__restrict__ val, double *__restrict__ mval, int *__restrict__ flag) {
+    __shared__ double Gs[SPAI1_WPB][SPAI1_SHORT * SPAI1_LD];
+    __shared__ int pbs[SPAI1_WPB][SPAI1_SHORT], pes[SPAI1_WPB][SPAI1_SHORT];
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+    double *G = Gs[w];
+    int *pb = pbs[w], *pe = pes[w];
+    const int64_t stride = (int64_t)gridDim.x * SPAI1_WPB;
+    for (int64_t row = (int64_t)blockIdx.x * SPAI1_WPB + w; row < n; row += stride) {
+        const int b0 = ptr[row];
+        const int k = ptr[row + 1] - b0;
+        if (k < 1 || k > SPAI1_SHORT) continue;  // wave-uniform
+        spai1_wave_sync();                       // the previous row is done with the LDS
+        // extents of the pattern's rows; lane a keeps rhs[a] (later y, then m)
+        double ra = 0.0;
+        if (lane < k) {
+            int c = col[b0 + lane];
+            int cb = ptr[c], ce = ptr[c + 1];
+            pb[lane] = cb;
+            pe[lane] = ce;
+            ra = spai1_entry(col, val, cb, ce, (int)row);
+        }
+        spai1_wave_sync();
+        // G: the a <= b pairs over the 64 lanes, mirrored
+        const int np = k * (k + 1) / 2;
+        for (int p = lane; p < np; p += WAVE) {
+            int a, b;
+            spai1_pair(p, &a, &b);
+            double s = spai1_row_dot(col, val, pb[a], pe[a], pb[b], pe[b]);
+            G[a * SPAI1_LD + b] = s;
+            G[b * SPAI1_LD + a] = s;
+        }
+        spai1_wave_sync();
+        // Cholesky G = L L^T, left-looking; lane a owns row a, L overwrites
+        // the lower triangle
+        const double d0 = lane < k ? G[lane * SPAI1_LD + lane] : 1.0;
+        bool singular = false;
+        for (int c = 0; c < k; ++c) {
+            double s = 0.0;
+            if (lane >= c && lane < k) {
+                s = G[lane * SPAI1_LD + c];
+                for (int j = 0; j < c; ++j) s -= G[lane * SPAI1_LD + j] * G[c * SPAI1_LD + j];
+            }
+            const double piv = __shfl(s, c, WAVE);
+            const double dc = __shfl(d0, c, WAVE);
+            if (piv <= (double)k * SPAI1_EPS * dc) {
+                singular = true;
+                break;
+            }
+            const double l = __builtin_sqrt(piv);
+            if (lane == c) G[c * SPAI1_LD + c] = l;
+            else if (lane > c && lane < k) G[lane * SPAI1_LD + c] = s / l;
+            spai1_wave_sync();
+        }
+        if (singular) {
+            if (lane == 0) atomicMax(flag, (int)row + 1);
+            continue;
+        }
+        // L y = rhs, then L^T m = y, on the lanes' registers
+        for (int c = 0; c < k; ++c) {
+            const double yc = __shfl(ra, c, WAVE) / G[c * SPAI1_LD + c];
+            if (lane == c) ra = yc;
+            else if (lane > c && lane < k) ra -= G[lane * SPAI1_LD + c] * yc;
+        }
+        for (int c = k - 1; c >= 0; --c) {
+            const double mc = __shfl(ra, c, WAVE) / G[c * SPAI1_LD + c];
+            if (lane == c) ra = mc;
+            else if (lane < c) ra -= G[c * SPAI1_LD + lane] * mc;
+        }
+        if (lane < k) mval[b0 + lane] = ra;
+    }
+}
+
+// Long tier: worklist rows (k > SPAI1_SHORT), one block per workspace slot.
+// A slot holds kmax*(kmax+2) doubles: the k x k upper factor U (G = U^T U,
+// row-major, so that the threads' reads along a row of U coalesce) and the
+// two solve vectors.
+__global__ __launch_bounds__(256) void spai1_long_k(
+    int64_t nlong, const int *__restrict__ list, const int *__restrict__ ptr,
+    const int *__restrict__ col, const double *__restrict__ val,
+    double *__restrict__ mval, int *__restrict__ flag, int kmax, double *work) {
+    __shared__ double sh[2];  // pivot of the column at hand, G's original diagonal entry
+    const int tid = threadIdx.x;
+    double *U = work + (int64_t)blockIdx.x * kmax * (kmax + 2);
+    double *r = U + (int64_t)kmax * kmax;
+    double *y = r + kmax;
+    for (int64_t w = blockIdx.x; w < nlong; w += gridDim.x) {
+        const int row = list[w];
+        const int b0 = ptr[row];
+        const int64_t k = ptr[row + 1] - b0;
+        if (k < 1 || k > kmax) {  // block-uniform; a worklist/kmax mismatch
+            if (tid == 0) atomicMax(flag, row + 1);
+            continue;
+        }
+        const int *I = col + b0;
+        __syncthreads();  // the previous row is done with the slot
+        for (int a = tid; a < k; a += 256) {
+            int c = I[a];
+            r[a] = spai1_entry(col, val, ptr[c], ptr[c + 1], row);
+        }
+        const int64_t np = k * (k + 1) / 2;
+        for (int64_t p = tid; p < np; p += 256) {
+            int a, b;
+            spai1_pair(p, &a, &b);
+            int ca = I[a], cb = I[b];
+            U[a * k + b] = spai1_row_dot(col, val, ptr[ca], ptr[ca + 1], ptr[cb], ptr[cb + 1]);
+        }
+        __syncthreads();
+        // column c of the factorisation fills row c of U
+        bool singular = false;
+        for (int64_t c = 0; c < k; ++c) {
+            for (int64_t a = c + tid; a < k; a += 256) {
+                double s = U[c * k + a];
+                for (int64_t j = 0; j < c; ++j) s -= U[j * k + a] * U[j * k + c];
+                if (a == c) {
+                    sh[0] = s;
+                    sh[1] = U[c * k + c];
+                }
+                U[c * k + a] = s;
+            }
+            __syncthreads();
+            const double piv = sh[0], dc = sh[1];
+            if (piv <= (double)k * SPAI1_EPS * dc) {  // block-uniform
+                singular = true;
+                break;
+            }
+            const double l = __builtin_sqrt(piv);
+            for (int64_t a = c + tid; a < k; a += 256)
+                U[c * k + a] = (a == c) ? l : U[c * k + a] / l;
+            __syncthreads();
+        }
+        if (singular) {
+            if (tid == 0) atomicMax(flag, row + 1);
+            continue;
+        }
+        // U^T y = rhs, column by column
+        for (int64_t c = 0; c < k; ++c) {
+            const double yc = r[c] / U[c * k + c];
+            if (tid == 0) y[c] = yc;
+            for (int64_t a = c + 1 + tid; a < k; a += 256) r[a] -= U[c * k + a] * yc;
+            __syncthreads();
+        }
+        // U m = y, column by column from the last
+        for (int64_t c = k - 1; c >= 0; --c) {
+            const double mc = y[c] / U[c * k + c];
+            if (tid == 0) mval[b0 + c] = mc;
+            for (int64_t j = tid; j < c; j += 256) y[j] -= U[j * k + c] * mc;
+            __syncthreads();
+        }
+    }
+}
+
+extern "C" int amg_spai1_short_max(void) { return SPAI1_SHORT; }
+
+// longrows/nlong: the rows longer than amg_spai1_short_max(); kmax: the
+// longest of them; work: slots * kmax*(kmax+2) doubles.  *flag is cleared
+// here and holds row+1 of a singular row afterwards (0: none).
+extern "C" int amg_setup_spai1(int64_t n, const int *ptr, const int *col, const double *val,
+                               double *mval, int *flag, int64_t nlong, const int *longrows,
+                               int kmax, int slots, double *work, hipStream_t s) {
+    hipError_t rc = hipMemsetAsync(flag, 0, sizeof(int), s);
+    if (rc != hipSuccess) return (int)rc;
+    if (n > 0)
+        spai1_short_k<<<nblk(n, SPAI1_WPB), 64 * SPAI1_WPB, 0, s>>>(n, ptr, col, val, mval,
+                                                                   flag);
+    if (nlong > 0) {
+        if (!longrows || !work || slots < 1 || kmax <= SPAI1_SHORT)
+            return (int)hipErrorInvalidValue;
+        int grid = (int)(nlong < slots ? nlong : slots);
+        spai1_long_k<<<grid, 256, 0, s>>>(nlong, longrows, ptr, col, val, mval, flag, kmax,
+                                          work);
+    }
     return (int)hipGetLastError();
 }
 

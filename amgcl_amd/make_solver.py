@@ -41,7 +41,8 @@ class MakeSolver:
         self.S = make_solver_component(
             A.nrows, prm.get("solver"), backend, inner_product
         )
-        # native C++ solve driver (HIP + AMG + diagonal smoothers + cg/bicgstab)
+        # native C++ solve driver (HIP + AMG + a smoother backend/native.py
+        # accepts + cg/bicgstab)
         self._native = None
         if inner_product is None and getattr(backend, "name", "") == "hip":
             from .backend.native import try_native

@@ -73,7 +73,10 @@ class Spai0(DiagonalSmootherBase):
 
 class Spai1:
     """SPAI-1 smoother: approximate inverse with A's sparsity
-    (parity: amgcl/relaxation/spai1.hpp:54). Apply: x += M (rhs - A x)."""
+    (parity: amgcl/relaxation/spai1.hpp:54). Apply: x += M (rhs - A x).
+
+    A device-resident level matrix is factored on the device
+    (hip_setup.spai1); a host matrix by _core.spai1 and uploaded."""
 
     gpu_supported = True
 
@@ -85,14 +88,20 @@ class Spai1:
         from ..matrix import CSR
 
         merge_params(self.defaults(), prm)
+        self.backend = backend
+        self.n = A.nrows
         if not isinstance(A, CSR):
             from ..backend import hip_setup
 
+            if not A.val.is_complex():
+                try:
+                    self.M = hip_setup.spai1(A)
+                    return
+                except OverflowError:
+                    pass  # a row too long for the device workspace: host routine
             A = hip_setup.download(A)
         mp, mc, mv = _core.spai1(A.nrows, A.ptr, A.col, A.val)
-        self.backend = backend
         self.M = backend.matrix(CSR(A.nrows, A.ncols, mp, mc, mv))
-        self.n = A.nrows
 
     def _step(self, A, rhs, x, tmp):
         b = self.backend
