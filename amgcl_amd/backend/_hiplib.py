@@ -136,6 +136,23 @@ _SPAI1_SIGS = {
                           ctypes.c_void_p, ctypes.c_void_p],
 }
 
+# Compact SELL-64 image (kernels.hip sell_k<..., COMPACT>): nrows, nslice,
+# moff, smask, ptr, scol, sval, then what the padded twin takes.  Kept beside
+# _SIGS for the same reason.
+_SELLC_SIGS = {
+    "amg_sellc_spmv_f64": [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 6
+                          + [ctypes.c_double, ctypes.c_double]
+                          + [ctypes.c_void_p] * 2,
+    "amg_sellc_residual_f64": [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 9,
+    "amg_sellc_relax_f64": [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 10,
+    # nrows, nslice, ptr, col, val, moff, smask, scol, sval, stream
+    "amg_sellc_fill_f64": [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 8,
+}
+for _op in ("spmv", "residual", "relax", "fill"):
+    _SELLC_SIGS[f"amg_sellc_{_op}_f32"] = _SELLC_SIGS[f"amg_sellc_{_op}_f64"]
+# padded slots, nnz, masks, slices, sizeof(value) -> 1 compact, 0 padded
+_SELLC_SIGS["amg_sell_compact_rule"] = [ctypes.c_int64] * 4 + [ctypes.c_int]
+
 
 def lib():
     global _LIB
@@ -153,7 +170,7 @@ def lib():
                 "--inplace` — GPU ops do not fall back to eager torch"
             )
         _LIB = ctypes.CDLL(path)
-        for name, argtypes in {**_SIGS, **_SPAI1_SIGS}.items():
+        for name, argtypes in {**_SIGS, **_SPAI1_SIGS, **_SELLC_SIGS}.items():
             fn = getattr(_LIB, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

@@ -26,7 +26,7 @@ def _stream():
 
 class DeviceCSR:
     __slots__ = ("nrows", "ncols", "ptr", "col", "val", "subw",
-                 "nslice", "soff", "scol", "sval", "srows")
+                 "nslice", "soff", "scol", "sval", "srows", "smask", "moff")
 
     def __init__(self, csr: CSR, device, subw=0):
         import torch
@@ -39,6 +39,7 @@ class DeviceCSR:
         self.subw = subw  # 0 = auto by mean row length
         self.nslice = 0
         self.soff = self.scol = self.sval = self.srows = None
+        self.smask = self.moff = None
 
     @classmethod
     def from_tensors(cls, nrows, ncols, ptr, col, val, subw=0):
@@ -49,6 +50,7 @@ class DeviceCSR:
         self.subw = subw
         self.nslice = 0
         self.soff = self.scol = self.sval = self.srows = None
+        self.smask = self.moff = None
         return self
 
     @property
@@ -62,9 +64,20 @@ class DeviceCSR:
                 self.val.data_ptr())
 
     @property
+    def sell_name(self):
+        """Kernel family of the SELL image this matrix carries: "sellc" for
+        the compact one, "sell" for the padded one."""
+        return "sellc" if self.smask is not None else "sell"
+
+    @property
     def sell_args(self):
-        """Leading arguments of the SELL kernels: nrows, nslice, soff, scol,
-        sval, srows (0 without a sigma-sort permutation)."""
+        """Leading arguments of the SELL kernels.  Padded image: nrows, nslice,
+        soff, scol, sval, srows (0 without a sigma-sort permutation).  Compact
+        image: nrows, nslice, moff, smask, ptr, scol, sval."""
+        if self.smask is not None:
+            return (self.nrows, self.nslice, self.moff.data_ptr(),
+                    self.smask.data_ptr(), self.ptr.data_ptr(), self.scol.data_ptr(),
+                    self.sval.data_ptr())
         return (self.nrows, self.nslice, self.soff.data_ptr(), self.scol.data_ptr(),
                 self.sval.data_ptr(),
                 self.srows.data_ptr() if self.srows is not None else 0)
@@ -72,11 +85,21 @@ class DeviceCSR:
     def bytes(self):
         b = (self.ptr.numel() + self.col.numel()) * 4 + self.val.numel() * 8
         if self.nslice:
-            b += self.soff.numel() * 8 + self.scol.numel() * 4
-            b += self.sval.numel() * self.sval.element_size()
+            b += self.scol.numel() * 4 + self.sval.numel() * self.sval.element_size()
+            if self.smask is not None:
+                b += (self.smask.numel() + self.moff.numel()) * 8
+            else:
+                b += self.soff.numel() * 8
         return b
 
-    def build_sell(self, sigma=0, sigma_min_rows=1 << 16, sigma_min_pad=1.08):
+    def _sell_fn(self, name):
+        import torch
+
+        sfx = "_f32" if self.val.dtype == torch.float32 else "_f64"
+        return getattr(lib(), "amg_" + name + sfx)
+
+    def build_sell(self, sigma=0, sigma_min_rows=1 << 16, sigma_min_pad=1.08,
+                   compact=False):
         """Build the SELL-64 image of this matrix (kernels.hip rationale:
         wave-native layout; lane = row, slices column-major).  The CSR arrays
         are kept — transfers and non-SELL paths still use them.
@@ -88,7 +111,15 @@ class DeviceCSR:
         which costs far more than the ~24% padding it saves.  Off by
         default; kept as an explicit option (and for matrices so ragged
         that padding dominates).  The sort is applied only above
-        sigma_min_rows rows and when padding exceeds sigma_min_pad x nnz."""
+        sigma_min_rows rows and when padding exceeds sigma_min_pad x nnz.
+
+        compact selects the pad-free image (kernels.hip, sell_k COMPACT):
+        scol/sval then hold exactly the nnz entries, smask one 64-bit lane
+        mask per slot and moff the slices' first masks; soff stays None.  No
+        row moves, so the vector accesses stay coalesced.  True / False force
+        one image, "auto" takes the compact one when the padding it removes
+        outweighs its masks (amg_sell_compact_pays, amg_common.h) and
+        AMGCL_SELL_PADDED is not set.  A sigma-sorted image is always padded."""
         if self.nslice:
             return self
         import os
@@ -115,6 +146,33 @@ class DeviceCSR:
         total = int(soff[-1].item())
         srows = None
         nnz = self.col.numel()
+        esize = self.val.element_size()
+        if sigma:
+            compact = False
+        elif compact == "auto":
+            compact = (not os.environ.get("AMGCL_SELL_PADDED")
+                       and bool(lib().amg_sell_compact_rule(total, nnz, total // 64,
+                                                            nslice, esize)))
+        if compact:
+            # values first: an odd nnz would misalign f64 values behind the
+            # int32 columns
+            moff = soff // 64
+            blob = torch.empty(nnz * (4 + esize), dtype=torch.uint8, device=dev)
+            sval = blob[: nnz * esize].view(self.val.dtype)
+            scol = blob[nnz * esize :].view(torch.int32)
+            # never empty: a null smask would read as "padded" in an OpDesc
+            smask = torch.empty(max(total // 64, 1), dtype=torch.int64, device=dev)
+            check(self._sell_fn("sellc_fill")(
+                n, nslice, self.ptr.data_ptr(), self.col.data_ptr(),
+                self.val.data_ptr(), moff.data_ptr(), smask.data_ptr(),
+                scol.data_ptr(), sval.data_ptr(), _stream()), "sellc_fill")
+            self.nslice, self.scol, self.sval = nslice, scol, sval
+            self.smask, self.moff = smask, moff
+            if dbg:
+                torch.cuda.synchronize()
+                print(f"[sell] n={n:>10} compact nnz={nnz:>11} masks={total // 64:>9} "
+                      f"{(time.perf_counter() - _t0) * 1e3:7.1f} ms", flush=True)
+            return self
         if sigma and total > sigma_min_pad * nnz and n > sigma_min_rows:
             # sigma-sorted slices: order rows by length inside sigma-sized
             # windows to cut the slice padding of ragged (coarse SA) levels;
@@ -144,18 +202,16 @@ class DeviceCSR:
         # writes the padding itself).  Measured: separate multi-GB
         # allocations stalled the GPU ~11 ms each at 512^3 (allocator
         # growth), see profiles/README.md round 2.
-        esize = self.val.element_size()
         blob = torch.empty(total * (4 + esize), dtype=torch.uint8, device=dev)
         scol = blob[: total * 4].view(torch.int32)
         sval = blob[total * 4 :].view(self.val.dtype)
         if dbg:
             _t3 = time.perf_counter()  # allocation
-        fn = (lib().amg_sell_fill_f32 if self.val.dtype == torch.float32
-              else lib().amg_sell_fill_f64)
-        check(fn(n, nslice, self.ptr.data_ptr(), self.col.data_ptr(),
-                 self.val.data_ptr(), soff.data_ptr(),
-                 srows.data_ptr() if srows is not None else 0,
-                 scol.data_ptr(), sval.data_ptr(), _stream()), "sell_fill")
+        check(self._sell_fn("sell_fill")(
+            n, nslice, self.ptr.data_ptr(), self.col.data_ptr(),
+            self.val.data_ptr(), soff.data_ptr(),
+            srows.data_ptr() if srows is not None else 0,
+            scol.data_ptr(), sval.data_ptr(), _stream()), "sell_fill")
         self.nslice, self.soff, self.scol, self.sval = nslice, soff, scol, sval
         self.srows = srows
         if dbg:
@@ -295,7 +351,7 @@ class HipBackend:
             check(lib().amg_spmv_c128(*A.csr_args, x.data_ptr(), a.real, a.imag, b.real,
                                       b.imag, y.data_ptr(), A.subw, _stream()), "cspmv")
         elif getattr(A, "nslice", 0):
-            check(self._fn("sell_spmv", A.sval)(*A.sell_args, x.data_ptr(), alpha, beta,
+            check(self._fn(A.sell_name + "_spmv", A.sval)(*A.sell_args, x.data_ptr(), alpha, beta,
                                                 y.data_ptr(), _stream()), "sell_spmv")
         else:
             check(self._fn("spmv", A.val)(*A.csr_args, x.data_ptr(), alpha, beta,
@@ -310,7 +366,7 @@ class HipBackend:
             check(lib().amg_residual_c128(*A.csr_args, *vecs, A.subw, _stream()),
                   "cresidual")
         elif getattr(A, "nslice", 0):
-            check(self._fn("sell_residual", A.sval)(*A.sell_args, *vecs, _stream()),
+            check(self._fn(A.sell_name + "_residual", A.sval)(*A.sell_args, *vecs, _stream()),
                   "sell_residual")
         else:
             check(self._fn("residual", A.val)(*A.csr_args, *vecs, A.subw, _stream()),
@@ -326,7 +382,7 @@ class HipBackend:
                   "crelax")
         elif getattr(A, "nslice", 0):
             # SELL relax writes x_new = x + M(rhs - Ax) into t, then copy back
-            check(self._fn("sell_relax", A.sval)(*A.sell_args, *vecs, _stream()),
+            check(self._fn(A.sell_name + "_relax", A.sval)(*A.sell_args, *vecs, _stream()),
                   "sell_relax")
             x.copy_(t)
             return

@@ -25,6 +25,8 @@ class OpDescC(ctypes.Structure):
         ("scol", ctypes.c_void_p),
         ("sval", ctypes.c_void_p),
         ("srows", ctypes.c_void_p),
+        ("smask", ctypes.c_void_p),
+        ("moff", ctypes.c_void_p),
     ]
 
 
@@ -130,7 +132,8 @@ def _ptr(t):
 
 def _op(dst, M, keep, subw=None):
     """Fill the OpDescC dst from the DeviceCSR M (CSR arrays, plus the SELL
-    image and its sigma permutation when M has them) and append every tensor
+    image, padded with its sigma permutation or compact with its masks, when
+    M has one) and append every tensor
     it now points at to keep.  subw overrides M's own; 0 lets the driver
     choose."""
     dst.nrows, dst.nnz = M.nrows, int(M.nnz)
@@ -141,7 +144,8 @@ def _op(dst, M, keep, subw=None):
         dst.nslice = M.nslice
         dst.soff, dst.scol, dst.sval = _ptr(M.soff), _ptr(M.scol), _ptr(M.sval)
         dst.srows = _ptr(M.srows)
-        keep.extend([M.soff, M.scol, M.sval, M.srows])
+        dst.smask, dst.moff = _ptr(M.smask), _ptr(M.moff)
+        keep.extend([M.soff, M.scol, M.sval, M.srows, M.smask, M.moff])
 
 
 class NativeDriver:

@@ -58,8 +58,9 @@ static inline int amg_pick_subw(int64_t nrows, int64_t nnz) {
 }
 
 // One sparse operator as the native solve driver (driver.hip) sees it: CSR
-// plus an optional SELL-64 image (see kernels.hip).  val/sval hold double, or
-// float in the fp32 hierarchy of a mixed-precision solve.
+// plus an optional SELL-64 image, padded or compact (see kernels.hip).
+// val/sval hold double, or float in the fp32 hierarchy of a mixed-precision
+// solve.
 struct OpDesc {
     int64_t nrows, nnz;
     const int *ptr;
@@ -71,7 +72,21 @@ struct OpDesc {
     const int *scol;
     const void *sval;
     const int *srows;  // optional sigma-sort permutation (slot -> row, < 0 = pad)
+    // compact (pad-free) image when smask is set: scol/sval then hold exactly
+    // nnz entries, smask one lane mask per slot, moff[nslice + 1] the slices'
+    // first masks; soff and srows are unused
+    const uint64_t *smask;
+    const int64_t *moff;
 };
+
+// Which SELL-64 image an operator gets: the compact one when the padding it
+// removes outweighs the masks and offsets it adds, in bytes.  slots = padded
+// slots (64 x the summed slice widths), nmask = the summed slice widths,
+// vbytes = sizeof(value).  The one statement of the rule, for every builder.
+static inline bool amg_sell_compact_pays(int64_t slots, int64_t nnz, int64_t nmask,
+                                         int64_t nslice, int vbytes) {
+    return (slots - nnz) * (4 + vbytes) > 8 * nmask + 8 * (nslice + 1);
+}
 
 // Per-level descriptor consumed by amg_driver_create; filled either from
 // Python (backend/native.py, torch tensors) or from the torch-free GPU C API

@@ -49,6 +49,39 @@ int amg_sell_relax_f32(int64_t nrows, int64_t nslice, const int64_t *soff, const
 int amg_sell_fill_f64(int64_t nrows, int64_t nslice, const int *ptr, const int *col,
                       const double *val, const int64_t *soff, const int *srows, int *scol,
                       double *sval, hipStream_t stream);
+// compact SELL-64 image (moff, smask, the CSR ptr, then the nnz-long scol/sval)
+int amg_sellc_spmv_f64(int64_t nrows, int64_t nslice, const int64_t *moff,
+                       const uint64_t *smask, const int *ptr, const int *col,
+                       const double *val, const double *x, double alpha, double beta,
+                       double *y, hipStream_t stream);
+int amg_sellc_spmv_f32(int64_t nrows, int64_t nslice, const int64_t *moff,
+                       const uint64_t *smask, const int *ptr, const int *col,
+                       const float *val, const float *x, double alpha, double beta,
+                       float *y, hipStream_t stream);
+int amg_sellc_residual_f64(int64_t nrows, int64_t nslice, const int64_t *moff,
+                           const uint64_t *smask, const int *ptr, const int *col,
+                           const double *val, const double *rhs, const double *x,
+                           double *r, hipStream_t stream);
+int amg_sellc_residual_f32(int64_t nrows, int64_t nslice, const int64_t *moff,
+                           const uint64_t *smask, const int *ptr, const int *col,
+                           const float *val, const float *rhs, const float *x, float *r,
+                           hipStream_t stream);
+int amg_sellc_relax_f64(int64_t nrows, int64_t nslice, const int64_t *moff,
+                        const uint64_t *smask, const int *ptr, const int *col,
+                        const double *val, const double *M, const double *rhs,
+                        const double *x, double *xn, hipStream_t stream);
+int amg_sellc_relax_f32(int64_t nrows, int64_t nslice, const int64_t *moff,
+                        const uint64_t *smask, const int *ptr, const int *col,
+                        const float *val, const float *M, const float *rhs,
+                        const float *x, float *xn, hipStream_t stream);
+int amg_sellc_fill_f64(int64_t nrows, int64_t nslice, const int *ptr, const int *col,
+                       const double *val, const int64_t *moff, uint64_t *smask,
+                       int *scol, double *sval, hipStream_t stream);
+int amg_sellc_fill_f32(int64_t nrows, int64_t nslice, const int *ptr, const int *col,
+                       const float *val, const int64_t *moff, uint64_t *smask, int *scol,
+                       float *sval, hipStream_t stream);
+int amg_sell_compact_rule(int64_t slots, int64_t nnz, int64_t nmask, int64_t nslice,
+                          int vbytes);
 int amg_axpby_f64(int64_t n, double a, const double *x, double b, double *y,
                   hipStream_t stream);
 int amg_axpby_f32(int64_t n, double a, const float *x, double b, float *y,

@@ -227,7 +227,8 @@ int scan_counts(int *p, int64_t n) {
 }
 
 // SELL-64 image of op's CSR arrays, built on the device into buffers of `own`
-// (same layout as DeviceCSR.build_sell)
+// (same layouts and the same choice between them as DeviceCSR.build_sell with
+// compact="auto")
 void build_sell_capi(Tracker &own, OpDesc &op) {
     const int64_t n = op.nrows, nslice = (n + 63) / 64;
     Tracker tmp;
@@ -239,7 +240,29 @@ void build_sell_capi(Tracker &own, OpDesc &op) {
         hipSuccess)
         throw DevSetupFail{};
     std::vector<int64_t> soff(nslice + 1, 0);
-    for (int64_t s = 0; s < nslice; ++s) soff[s + 1] = soff[s] + (int64_t)wh[s] * 64;
+    for (int64_t s = 0; s < nslice; ++s) soff[s + 1] = soff[s] + (int64_t)wh[s];
+    const int64_t nmask = soff[nslice];
+    const bool compact =
+        !getenv("AMGCL_SELL_PADDED") &&
+        amg_sell_compact_pays(nmask * 64, op.nnz, nmask, nslice, (int)sizeof(double));
+    trace("sell_compact", compact, nmask);
+    if (compact) {  // soff counts masks: it is moff
+        int64_t *moff_d = own.alloc<int64_t>(nslice + 1);
+        if (!upload_bytes(moff_d, soff.data(), (nslice + 1) * sizeof(int64_t)))
+            throw DevSetupFail{};
+        uint64_t *smask = own.alloc<uint64_t>(nmask);
+        int *scol = own.alloc<int>(op.nnz);
+        double *sval = own.alloc<double>(op.nnz);
+        dev_check(amg_sellc_fill_f64(n, nslice, op.ptr, op.col, (const double *)op.val,
+                                     moff_d, smask, scol, sval, 0));
+        op.nslice = nslice;
+        op.moff = moff_d;
+        op.smask = smask;
+        op.scol = scol;
+        op.sval = sval;
+        return;
+    }
+    for (int64_t s = 0; s <= nslice; ++s) soff[s] *= 64;
     int64_t total = soff[nslice];
     int64_t *soff_d = own.alloc<int64_t>(nslice + 1);
     if (!upload_bytes(soff_d, soff.data(), (nslice + 1) * sizeof(int64_t)))

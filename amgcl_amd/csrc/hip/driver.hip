@@ -46,6 +46,9 @@ AMG_BY_TYPE(gemv)
 AMG_BY_TYPE(sell_spmv)
 AMG_BY_TYPE(sell_residual)
 AMG_BY_TYPE(sell_relax)
+AMG_BY_TYPE(sellc_spmv)
+AMG_BY_TYPE(sellc_residual)
+AMG_BY_TYPE(sellc_relax)
 AMG_BY_TYPE(axpby)
 AMG_BY_TYPE(vmul)
 AMG_BY_TYPE(fill)
@@ -123,10 +126,14 @@ struct Driver {
     } while (0)
 
 // y = alpha op x + beta y and r = rhs - op x, through the operator's SELL
-// image when it has one, else CSR: the only place that choice is made
+// image when it has one (compact if smask is set, else padded), else CSR:
+// the only place that choice is made
 template <typename T>
 static int op_spmv(Driver *D, const OpDesc &op, const T *x, double alpha, double beta,
                    T *y) {
+    if (op.nslice && op.smask)
+        return sellc_spmv<T>(op.nrows, op.nslice, op.moff, op.smask, op.ptr, op.scol,
+                             (const T *)op.sval, x, alpha, beta, y, D->stream);
     if (op.nslice)
         return sell_spmv<T>(op.nrows, op.nslice, op.soff, op.scol, (const T *)op.sval,
                             op.srows, x, alpha, beta, y, D->stream);
@@ -136,6 +143,9 @@ static int op_spmv(Driver *D, const OpDesc &op, const T *x, double alpha, double
 
 template <typename T>
 static int op_residual(Driver *D, const OpDesc &op, const T *rhs, const T *x, T *r) {
+    if (op.nslice && op.smask)
+        return sellc_residual<T>(op.nrows, op.nslice, op.moff, op.smask, op.ptr, op.scol,
+                                 (const T *)op.sval, rhs, x, r, D->stream);
     if (op.nslice)
         return sell_residual<T>(op.nrows, op.nslice, op.soff, op.scol,
                                 (const T *)op.sval, op.srows, rhs, x, r, D->stream);
@@ -259,8 +269,12 @@ static int relax_swap(Driver *D, const LevelDesc &L, const T *rhs, T **x, T **xn
     const OpDesc &A = L.A;
     const T *M = (const T *)L.M;
     if (A.nslice) {
-        CHK(sell_relax<T>(A.nrows, A.nslice, A.soff, A.scol, (const T *)A.sval, A.srows,
-                          M, rhs, *x, *xn, D->stream));
+        if (A.smask)
+            CHK(sellc_relax<T>(A.nrows, A.nslice, A.moff, A.smask, A.ptr, A.scol,
+                               (const T *)A.sval, M, rhs, *x, *xn, D->stream));
+        else
+            CHK(sell_relax<T>(A.nrows, A.nslice, A.soff, A.scol, (const T *)A.sval,
+                              A.srows, M, rhs, *x, *xn, D->stream));
         std::swap(*x, *xn);
         return 0;
     }
@@ -496,7 +510,7 @@ extern "C" int amg_desc_layout(int64_t *out, int cap) {
     const size_t v[] = {
         sizeof(OpDesc), sizeof(LevelDesc),
         OP(nrows), OP(nnz), OP(ptr), OP(col), OP(val), OP(subw), OP(nslice), OP(soff), OP(scol),
-        OP(sval), OP(srows),
+        OP(sval), OP(srows), OP(smask), OP(moff),
         LV(A), LV(P), LV(R), LV(M), LV(f), LV(u), LV(t), LV(cheb_degree), LV(cheb_theta),
         LV(cheb_delta), LV(cheb_sigma1), LV(cheb_d), LV(bsize), LV(nbrows), LV(bptr), LV(bcol),
         LV(bval), LV(spai1), LV(ilu_iters), LV(ilu_damping), LV(ilu_jdamping), LV(ilu_L), LV(ilu_U),

@@ -199,23 +199,75 @@ extern "C" int amg_relax_diag_f32(int64_t nrows, int64_t nnz, const int *ptr,
 // slot).  Sorting rows by length inside sigma-sized windows cuts the slice
 // padding of ragged coarse levels; the permutation stays within a window,
 // so the scattered x/rhs/y accesses remain L2-local.
-template <typename T, int MODE>  // 0: y=aAx+by  1: r=rhs-Ax  2: xn=x+M(rhs-Ax)
+//
+// COMPACT: the pad-free image.  Same mapping (slice = 64 consecutive rows,
+// lane = row, slot i = the row's i-th CSR entry) but a slot stores only the
+// lanes whose row is longer than i, packed in lane order, and one 64-bit lane
+// mask per slot says which lanes those are.  moff[s] .. moff[s+1] index the
+// slice's masks (its width w may be 0); the slice's entries start at the CSR
+// ptr[64 s], so the image holds exactly nnz entries.  A lane's products are
+// summed in slot order as in the padded kernel; only the trailing 0 * x[0]
+// terms of the padding are gone.  The slice index is made wave-uniform, so
+// masks and the running entry offset stay in scalar registers; the masks of
+// SELLC_U slots are fetched ahead of the loads that depend on them.
+#define SELLC_U 4
+template <typename T, int MODE, bool COMPACT>  // 0: y=aAx+by  1: r=rhs-Ax  2: xn=x+M(rhs-Ax)
 __global__ void sell_k(int64_t nrows, int64_t nslice,
-                       const int64_t *__restrict__ soff, const int *__restrict__ col,
+                       const int64_t *__restrict__ soff,  // COMPACT: moff
+                       const int *__restrict__ col,
                        const T *__restrict__ val, const int *__restrict__ srows,
+                       const uint64_t *__restrict__ smask, const int *__restrict__ ptr,
                        const T *__restrict__ x,
                        double alpha, double beta, const T *__restrict__ rhs,
                        const T *__restrict__ M, T *__restrict__ y) {
     const int wpb = blockDim.x / WAVE;
     int wid = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+    if (COMPACT) wid = __builtin_amdgcn_readfirstlane(wid);
     int64_t s = (int64_t)blockIdx.x * wpb + wid;
     int64_t sstride = (int64_t)gridDim.x * wpb;
     for (; s < nslice; s += sstride) {
-        int64_t beg = soff[s], end = soff[s + 1];
         double acc = 0.0;
-        for (int64_t j = beg + lane; j < end; j += WAVE)
-            acc += (double)val[j] * (double)x[col[j]];
-        int64_t row = srows ? (int64_t)srows[s * WAVE + lane] : s * WAVE + lane;
+        if (COMPACT) {
+            const int64_t mbeg = soff[s];
+            const int w = (int)(soff[s + 1] - mbeg);
+            int64_t off = ptr[s * WAVE];
+            for (int i = 0; i < w; i += SELLC_U) {
+                uint64_t m[SELLC_U];
+                int c[SELLC_U];
+                T v[SELLC_U];
+#pragma unroll
+                for (int k = 0; k < SELLC_U; ++k) m[k] = i + k < w ? smask[mbeg + i + k] : 0;
+#pragma unroll
+                for (int k = 0; k < SELLC_U; ++k) {
+                    c[k] = 0;
+                    v[k] = (T)0;
+                    if ((m[k] >> lane) & 1) {
+                        // entries of this slot below this lane: the mbcnt pair
+                        const int64_t j = off + __builtin_amdgcn_mbcnt_hi(
+                            (unsigned)(m[k] >> 32),
+                            __builtin_amdgcn_mbcnt_lo((unsigned)m[k], 0u));
+                        c[k] = col[j];
+                        v[k] = val[j];
+                    }
+                    off += __popcll(m[k]);
+                }
+                // gathers of all SELLC_U slots in flight before the first sum;
+                // an inactive lane adds 0 * 0
+                T xv[SELLC_U];
+#pragma unroll
+                for (int k = 0; k < SELLC_U; ++k) {
+                    xv[k] = (T)0;
+                    if ((m[k] >> lane) & 1) xv[k] = x[c[k]];
+                }
+#pragma unroll
+                for (int k = 0; k < SELLC_U; ++k) acc += (double)v[k] * (double)xv[k];
+            }
+        } else {
+            int64_t beg = soff[s], end = soff[s + 1];
+            for (int64_t j = beg + lane; j < end; j += WAVE)
+                acc += (double)val[j] * (double)x[col[j]];
+        }
+        int64_t row = (!COMPACT && srows) ? (int64_t)srows[s * WAVE + lane] : s * WAVE + lane;
         if (row >= 0 && row < nrows) {
             if (MODE == 0)
                 y[row] = (T)(beta == 0.0 ? alpha * acc
@@ -233,8 +285,18 @@ template <typename T, int MODE>
 static int launch_sell(int64_t nrows, int64_t nslice, const int64_t *soff, const int *col,
                        const T *val, const int *srows, const T *x, double alpha,
                        double beta, const T *rhs, const T *M, T *y, hipStream_t stream) {
-    sell_k<T, MODE><<<amg_nblocks(nslice * WAVE), 256, 0, stream>>>(
-        nrows, nslice, soff, col, val, srows, x, alpha, beta, rhs, M, y);
+    sell_k<T, MODE, false><<<amg_nblocks(nslice * WAVE), 256, 0, stream>>>(
+        nrows, nslice, soff, col, val, srows, nullptr, nullptr, x, alpha, beta, rhs, M, y);
+    return (int)hipGetLastError();
+}
+
+template <typename T, int MODE>
+static int launch_sellc(int64_t nrows, int64_t nslice, const int64_t *moff,
+                        const uint64_t *smask, const int *ptr, const int *col,
+                        const T *val, const T *x, double alpha, double beta, const T *rhs,
+                        const T *M, T *y, hipStream_t stream) {
+    sell_k<T, MODE, true><<<amg_nblocks(nslice * WAVE), 256, 0, stream>>>(
+        nrows, nslice, moff, col, val, nullptr, smask, ptr, x, alpha, beta, rhs, M, y);
     return (int)hipGetLastError();
 }
 
@@ -339,6 +401,92 @@ extern "C" int amg_sell_fill_f32(int64_t nrows, int64_t nslice, const int *ptr,
                                  const int64_t *soff, const int *srows, int *scol,
                                  float *sval, hipStream_t stream) {
     return launch_sell_fill(nrows, nslice, ptr, col, val, soff, srows, scol, sval, stream);
+}
+
+// Compact-image twins of the entry points above (no sigma permutation: that
+// form exists only to cut padding).
+#define AMG_SELLC_ENTRIES(T, SFX)                                                          \
+    extern "C" int amg_sellc_spmv_##SFX(int64_t nrows, int64_t nslice, const int64_t *moff, \
+                                        const uint64_t *smask, const int *ptr,             \
+                                        const int *col, const T *val, const T *x,          \
+                                        double alpha, double beta, T *y,                   \
+                                        hipStream_t stream) {                              \
+        return launch_sellc<T, 0>(nrows, nslice, moff, smask, ptr, col, val, x, alpha,     \
+                                  beta, nullptr, nullptr, y, stream);                      \
+    }                                                                                      \
+    extern "C" int amg_sellc_residual_##SFX(int64_t nrows, int64_t nslice,                 \
+                                            const int64_t *moff, const uint64_t *smask,    \
+                                            const int *ptr, const int *col, const T *val,  \
+                                            const T *rhs, const T *x, T *r,                \
+                                            hipStream_t stream) {                          \
+        return launch_sellc<T, 1>(nrows, nslice, moff, smask, ptr, col, val, x, 0.0, 0.0,  \
+                                  rhs, nullptr, r, stream);                                \
+    }                                                                                      \
+    extern "C" int amg_sellc_relax_##SFX(int64_t nrows, int64_t nslice,                    \
+                                         const int64_t *moff, const uint64_t *smask,       \
+                                         const int *ptr, const int *col, const T *val,     \
+                                         const T *M, const T *rhs, const T *x, T *xn,      \
+                                         hipStream_t stream) {                             \
+        return launch_sellc<T, 2>(nrows, nslice, moff, smask, ptr, col, val, x, 0.0, 0.0,  \
+                                  rhs, M, xn, stream);                                     \
+    }                                                                                      \
+    extern "C" int amg_sellc_fill_##SFX(int64_t nrows, int64_t nslice, const int *ptr,     \
+                                        const int *col, const T *val, const int64_t *moff, \
+                                        uint64_t *smask, int *scol, T *sval,               \
+                                        hipStream_t stream) {                              \
+        sellc_fill_k<T><<<amg_nblocks(nslice * WAVE), 256, 0, stream>>>(                   \
+            nrows, nslice, ptr, col, val, moff, smask, scol, sval);                        \
+        return (int)hipGetLastError();                                                     \
+    }
+
+// CSR -> compact SELL-64 fill, one wave per slice like sell_fill_k.  Slot i's
+// mask is the ballot of i < len; lane 0 stores it, the active lanes store
+// their entry at the slice's running offset plus their rank in the mask.
+// moff must give each slice its longest row's length as width.
+template <typename T>
+__global__ void sellc_fill_k(int64_t nrows, int64_t nslice, const int *__restrict__ ptr,
+                             const int *__restrict__ col, const T *__restrict__ val,
+                             const int64_t *__restrict__ moff,
+                             uint64_t *__restrict__ smask, int *__restrict__ scol,
+                             T *__restrict__ sval) {
+    const int wpb = blockDim.x / WAVE;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+    const int lane = threadIdx.x & (WAVE - 1);
+    int64_t s = (int64_t)blockIdx.x * wpb + wid;
+    int64_t sstride = (int64_t)gridDim.x * wpb;
+    for (; s < nslice; s += sstride) {
+        const int64_t row = s * WAVE + lane;
+        int b = 0, len = 0;
+        if (row < nrows) {
+            b = ptr[row];
+            len = ptr[row + 1] - b;
+        }
+        const int64_t mbeg = moff[s];
+        const int w = (int)(moff[s + 1] - mbeg);
+        int64_t off = ptr[s * WAVE];
+        for (int i = 0; i < w; ++i) {
+            const uint64_t m = __ballot(i < len);
+            if (lane == 0) smask[mbeg + i] = m;
+            if (i < len) {
+                const int64_t j = off + __builtin_amdgcn_mbcnt_hi(
+                    (unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                scol[j] = col[b + i];
+                sval[j] = val[b + i];
+            }
+            off += __popcll(m);
+        }
+    }
+}
+
+AMG_SELLC_ENTRIES(double, f64)
+AMG_SELLC_ENTRIES(float, f32)
+#undef AMG_SELLC_ENTRIES
+
+// Which image an operator gets (amg_sell_compact_pays, amg_common.h), for the
+// Python builder.
+extern "C" int amg_sell_compact_rule(int64_t slots, int64_t nnz, int64_t nmask,
+                                     int64_t nslice, int vbytes) {
+    return amg_sell_compact_pays(slots, nnz, nmask, nslice, vbytes) ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------

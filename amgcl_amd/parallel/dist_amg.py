@@ -93,10 +93,10 @@ class DistAMG:
 
         def conv(M):
             if isinstance(M, DeviceCSR) and M.nrows >= 500_000:
-                M.build_sell()
+                M.build_sell(compact="auto")
             elif isinstance(M, DistMatrix) and isinstance(M.A_loc, DeviceCSR) \
                     and M.A_loc.nrows >= 500_000:
-                M.A_loc.build_sell()
+                M.A_loc.build_sell(compact="auto")
 
         for L in self.levels:
             for name in ("A", "P", "R"):

@@ -68,6 +68,11 @@ class AMG:
             "sell_min_rows": 500000,
             "sell_min_mean": 0.0,
             "sell_transfers": True,  # also convert P/R transfer operators
+            # Which image: "auto" stores an operator pad-free (compact) when
+            # the padding that removes outweighs the lane masks it adds (the
+            # ragged P, R and coarse A; not the 7-point fine level), True /
+            # False force one.  AMGCL_SELL_PADDED=1 makes "auto" padded.
+            "sell_compact": "auto",
         }
 
     def __init__(self, A, prm=None, backend=None):
@@ -114,6 +119,7 @@ class AMG:
 
         min_rows = int(prm["sell_min_rows"])
         min_mean = float(prm["sell_min_mean"])
+        compact = prm["sell_compact"]
 
         def eligible(M):
             if not isinstance(M, DeviceCSR) or M.nrows < min_rows:
@@ -124,11 +130,11 @@ class AMG:
 
         for lvl in self.levels:
             if eligible(lvl.A):
-                lvl.A.build_sell()
+                lvl.A.build_sell(compact=compact)
             if prm["sell_transfers"]:
                 for M in (lvl.P, lvl.R):
                     if M is not None and eligible(M):
-                        M.build_sell()
+                        M.build_sell(compact=compact)
 
     def rebuild(self, A_new):
         """Reuse the transfer operators for a matrix with changed coefficients

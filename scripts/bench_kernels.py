@@ -29,6 +29,30 @@ def timeit(fn, iters=20):
     return (time.perf_counter() - t0) / iters
 
 
+def sell_images(hip, label, M):
+    """One line per SELL-64 image (padded, compact) of M: y = M x time and the
+    bandwidth over the bytes that image reads."""
+    from amgcl_amd.backend.hip import DeviceCSR
+
+    nnz = int(M.nnz)
+    x = torch.rand(M.ncols, dtype=torch.float64, device=hip.device)
+    y = torch.zeros(M.nrows, dtype=torch.float64, device=hip.device)
+    vecs = (min(nnz, M.ncols) + M.nrows) * 8
+    for compact in (False, True):
+        S = DeviceCSR.from_tensors(M.nrows, M.ncols, M.ptr, M.col, M.val)
+        S.build_sell(compact=compact)
+        if compact:
+            nbytes = nnz * 12 + (S.smask.numel() + S.moff.numel()) * 8 + S.nslice * 4
+        else:
+            nbytes = S.scol.numel() * 12 + S.soff.numel() * 8
+        dt = timeit(lambda: hip.spmv(1.0, S, x, 0.0, y))
+        kind = "compact" if compact else f"padded x{S.scol.numel() / max(nnz, 1):4.2f}"
+        print(f"   {label} n={M.nrows:>9} nnz={nnz:>10} SELL {kind:<12}: "
+              f"{dt * 1e6:8.1f} us  {(nbytes + vecs) / 1e9 / dt:5.0f} GB/s  "
+              f"image {nbytes:>12} B")
+        del S
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=384)
@@ -95,7 +119,7 @@ def main():
                 Ad.build_sell()
             except Exception as e:
                 print(f"   (sell build failed: {e})")
-        if Ad.nslice:
+        if Ad.nslice and Ad.smask is None:
             pad = Ad.sval.numel() / max(nnz, 1)
             dt = timeit(lambda: hip.spmv(1.0, Ad, x, 0.0, y))
             s_spmv = gb_spmv / dt
@@ -105,6 +129,13 @@ def main():
             s_res = (gb_spmv + n * 8 / 1e9) / dt
             print(f"   SELL (pad x{pad:4.2f}): spmv {s_spmv:5.0f}  "
                   f"relax {s_rel:5.0f}  residual {s_res:5.0f} GB/s")
+        # padded against compact image of A, P and R, bytes counted as each
+        # image really reads them: slots (padded) or nnz (compact) x 12, the
+        # slice offsets or masks, and both vectors once
+        for name, M in (("A", Ad), ("P", lvl.P), ("R", lvl.R)):
+            if M is None or M.nrows < 2000:
+                continue
+            sell_images(hip, f"L{li} {name}", M)
 
     n = amg.levels[0].rows
     x = torch.rand(n, dtype=torch.float64, device=hip.device)
