@@ -14,7 +14,21 @@
 // scalar row per lane within the block row, x-block reuse for free).
 //
 // Layout: block values row-major within each block, blocks in CSR order.
-// B lanes cooperate on one block row (lane = scalar row within the block).
+//
+// B lanes cooperate on one block row (lane = scalar row within the block),
+// for every block size 2..8.
+//
+// MEASURED (profiles/bsr_wide_blocks.md): at B = 5..8 a second mapping was
+// built and timed against this one, a wave per block row (then per chunk of 8
+// block rows walked as one stream) with lane = one (r, c) entry of the block,
+// so that every value load is the contiguous image of a block and one LDS
+// reduction closes each block row.  It lost at 6, 7 and 8 (0.65x, 0.90x,
+// 0.85x of this mapping's bandwidth on 7 blocks a row) and tied at 5: a lane
+// then does one FMA per block where a lane here does B, so the address
+// arithmetic and loop control per block are spread over B times fewer
+// products and the kernel is bound by instruction issue, not by memory.  The
+// lane-per-scalar-row loads, B consecutive doubles a lane, are wide enough
+// (dwordx4) to keep the memory system busy without being wave-contiguous.
 
 #include <hip/hip_runtime.h>
 
@@ -115,23 +129,44 @@ __global__ void blkdiag_vmul_k(int64_t nbrows, const double *__restrict__ M,
     }
 }
 
+// Grid of the lane-per-scalar-row kernels.  B = 2..4 launch what they always
+// have.  At B = 5..8 a capped grid is cut to a multiple of B blocks: tid / B
+// and the rounded-down stride of the kernels otherwise let the partial block
+// row at the end of one grid-stride pass meet the first block row of the next,
+// and an element updated twice is wrong as soon as beta != 0.  An uncapped
+// grid covers every block row in its first pass.
+static inline int bsr_grid(int64_t nbrows, int bsize) {
+    const int64_t work = nbrows * bsize;
+    int grid = nblk_b(work);
+    if (bsize > 4 && (int64_t)grid * 256 < work) grid -= grid % bsize;
+    return grid;
+}
+
 #define BSR_LAUNCH(kname, ...)                                              \
     switch (bsize) {                                                        \
         case 2: kname<2><<<grid, 256, 0, s>>>(__VA_ARGS__); break;          \
         case 3: kname<3><<<grid, 256, 0, s>>>(__VA_ARGS__); break;          \
         case 4: kname<4><<<grid, 256, 0, s>>>(__VA_ARGS__); break;          \
+        case 5: kname<5><<<grid, 256, 0, s>>>(__VA_ARGS__); break;          \
+        case 6: kname<6><<<grid, 256, 0, s>>>(__VA_ARGS__); break;          \
+        case 7: kname<7><<<grid, 256, 0, s>>>(__VA_ARGS__); break;          \
+        case 8: kname<8><<<grid, 256, 0, s>>>(__VA_ARGS__); break;          \
         default: return (int)hipErrorInvalidValue;                          \
     }
 
 extern "C" int amg_bsr_spmv_f64(int64_t nbrows, int bsize, const int *ptr, const int *col,
                                 const double *val, const double *x, double alpha,
                                 double beta, double *y, hipStream_t s) {
-    int grid = nblk_b(nbrows * bsize);
+    int grid = bsr_grid(nbrows, bsize);
     if (beta == 0.0) {
         switch (bsize) {
             case 2: bsr_spmv_k<2, true><<<grid, 256, 0, s>>>(nbrows, ptr, col, val, x, alpha, beta, y); break;
             case 3: bsr_spmv_k<3, true><<<grid, 256, 0, s>>>(nbrows, ptr, col, val, x, alpha, beta, y); break;
             case 4: bsr_spmv_k<4, true><<<grid, 256, 0, s>>>(nbrows, ptr, col, val, x, alpha, beta, y); break;
+            case 5: bsr_spmv_k<5, true><<<grid, 256, 0, s>>>(nbrows, ptr, col, val, x, alpha, beta, y); break;
+            case 6: bsr_spmv_k<6, true><<<grid, 256, 0, s>>>(nbrows, ptr, col, val, x, alpha, beta, y); break;
+            case 7: bsr_spmv_k<7, true><<<grid, 256, 0, s>>>(nbrows, ptr, col, val, x, alpha, beta, y); break;
+            case 8: bsr_spmv_k<8, true><<<grid, 256, 0, s>>>(nbrows, ptr, col, val, x, alpha, beta, y); break;
             default: return (int)hipErrorInvalidValue;
         }
     } else {
@@ -139,6 +174,10 @@ extern "C" int amg_bsr_spmv_f64(int64_t nbrows, int bsize, const int *ptr, const
             case 2: bsr_spmv_k<2, false><<<grid, 256, 0, s>>>(nbrows, ptr, col, val, x, alpha, beta, y); break;
             case 3: bsr_spmv_k<3, false><<<grid, 256, 0, s>>>(nbrows, ptr, col, val, x, alpha, beta, y); break;
             case 4: bsr_spmv_k<4, false><<<grid, 256, 0, s>>>(nbrows, ptr, col, val, x, alpha, beta, y); break;
+            case 5: bsr_spmv_k<5, false><<<grid, 256, 0, s>>>(nbrows, ptr, col, val, x, alpha, beta, y); break;
+            case 6: bsr_spmv_k<6, false><<<grid, 256, 0, s>>>(nbrows, ptr, col, val, x, alpha, beta, y); break;
+            case 7: bsr_spmv_k<7, false><<<grid, 256, 0, s>>>(nbrows, ptr, col, val, x, alpha, beta, y); break;
+            case 8: bsr_spmv_k<8, false><<<grid, 256, 0, s>>>(nbrows, ptr, col, val, x, alpha, beta, y); break;
             default: return (int)hipErrorInvalidValue;
         }
     }
@@ -148,7 +187,7 @@ extern "C" int amg_bsr_spmv_f64(int64_t nbrows, int bsize, const int *ptr, const
 extern "C" int amg_bsr_residual_f64(int64_t nbrows, int bsize, const int *ptr,
                                     const int *col, const double *val, const double *rhs,
                                     const double *x, double *r, hipStream_t s) {
-    int grid = nblk_b(nbrows * bsize);
+    int grid = bsr_grid(nbrows, bsize);
     BSR_LAUNCH(bsr_residual_k, nbrows, ptr, col, val, rhs, x, r)
     return (int)hipGetLastError();
 }
@@ -156,14 +195,14 @@ extern "C" int amg_bsr_residual_f64(int64_t nbrows, int bsize, const int *ptr,
 extern "C" int amg_bsr_relax_f64(int64_t nbrows, int bsize, const int *ptr, const int *col,
                                  const double *val, const double *M, const double *rhs,
                                  const double *x, double *t, hipStream_t s) {
-    int grid = nblk_b(nbrows * bsize);
+    int grid = bsr_grid(nbrows, bsize);
     BSR_LAUNCH(bsr_relax_k, nbrows, ptr, col, val, M, rhs, x, t)
     return (int)hipGetLastError();
 }
 
 extern "C" int amg_blkdiag_vmul_f64(int64_t nbrows, int bsize, const double *M,
                                     const double *x, double *y, hipStream_t s) {
-    int grid = nblk_b(nbrows * bsize);
+    int grid = bsr_grid(nbrows, bsize);
     BSR_LAUNCH(blkdiag_vmul_k, nbrows, M, x, y)
     return (int)hipGetLastError();
 }

@@ -87,6 +87,9 @@ class AMG:
             raise ValueError(f"precision must be fp64|mixed, got '{p['precision']}'")
         if int(p["block_value"]) < 0:
             raise ValueError("block_value must be >= 0")
+        if int(p["block_value"]) > 8:
+            raise ValueError("block_value must be <= 8 (the BSR kernels' "
+                             "largest block)")
         if int(p["ncycle"]) < 1 or int(p["pre_cycles"]) < 1:
             raise ValueError("ncycle and pre_cycles must be >= 1")
         if int(p["npre"]) < 0 or int(p["npost"]) < 0:

@@ -72,8 +72,9 @@ class AsBlock:
         if backend.name == "cpu":
             self.M = np.ascontiguousarray(M)
         else:
-            if B not in (2, 3, 4):
-                raise ValueError("as_block on the HIP backend supports B in {2,3,4}")
+            if not 2 <= B <= 8:
+                raise ValueError("as_block on the HIP backend supports "
+                                 "block_size 2..8")
             self.M = backend.from_host(M.ravel())
             self._t2 = backend.vector(self.n)
 
