@@ -153,6 +153,26 @@ for _op in ("spmv", "residual", "relax", "fill"):
 # padded slots, nnz, masks, slices, sizeof(value) -> 1 compact, 0 padded
 _SELLC_SIGS["amg_sell_compact_rule"] = [ctypes.c_int64] * 4 + [ctypes.c_int]
 
+# Fused SELL passes (kernels.hip sell_k modes 3 to 5) and the zero-guess smooth
+# they absorb.  One entry serves both images: nrows, nslice, off (soff or moff),
+# scol, sval, srows (or 0), smask (or 0), ptr (or 0), then the mode's vectors.
+# Kept beside _SIGS for the same reason.
+_IMG = [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 6
+_FUSED_SIGS = {
+    # n, M, rhs, xn, stream
+    "amg_relax_zero_f64": [ctypes.c_int64] + [ctypes.c_void_p] * 4,
+    # image, M, rhs, u, t, stream
+    "amg_sell_zero_residual_f64": _IMG + [ctypes.c_void_p] * 5,
+    # image, M, rhs, x, xn, out, stream
+    "amg_sell_relax_dot_f64": _IMG + [ctypes.c_void_p] * 6,
+    # image, s, p, beta, first, p_new, q, out, stream
+    "amg_sell_pupdate_spmv_dot_f64": _IMG + [ctypes.c_void_p] * 2
+                                     + [ctypes.c_double, ctypes.c_int]
+                                     + [ctypes.c_void_p] * 4,
+}
+for _op in ("relax_zero", "sell_zero_residual"):
+    _FUSED_SIGS[f"amg_{_op}_f32"] = _FUSED_SIGS[f"amg_{_op}_f64"]
+
 
 def lib():
     global _LIB
@@ -170,7 +190,7 @@ def lib():
                 "--inplace` — GPU ops do not fall back to eager torch"
             )
         _LIB = ctypes.CDLL(path)
-        for name, argtypes in {**_SIGS, **_SPAI1_SIGS, **_SELLC_SIGS}.items():
+        for name, argtypes in {**_SIGS, **_SPAI1_SIGS, **_SELLC_SIGS, **_FUSED_SIGS}.items():
             fn = getattr(_LIB, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

@@ -114,6 +114,13 @@ def _bind():
                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]
         )
         L.amg_driver_cg.restype = ctypes.c_int
+        # ... s_swap, p_swap, x_is_zero, tol, ...
+        L.amg_driver_cg_fused.argtypes = (
+            [ctypes.c_void_p] + [ctypes.c_void_p] * 8
+            + [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+               ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]
+        )
+        L.amg_driver_cg_fused.restype = ctypes.c_int
         L.amg_driver_bicgstab.argtypes = (
             [ctypes.c_void_p] + [ctypes.c_void_p] * 10
             + [ctypes.c_double, ctypes.c_double, ctypes.c_int,
@@ -262,20 +269,24 @@ class NativeDriver:
         )
         if not self.handle:
             raise RuntimeError("amg_driver_create failed")
-        nwork = 5 if solver_kind == "cg" else 8
+        # cg: r, s, p, q, s_swap and p_swap, the partner of the fused p update
+        nwork = 6 if solver_kind == "cg" else 8
         self._work = [torch.empty(n0, dtype=torch.float64, device=backend.device)
                       for _ in range(nwork)]
         self._descs = descs
 
-    def solve(self, rhs, x):
+    def solve(self, rhs, x, x_is_zero=False):
+        """x_is_zero: the caller made x itself and it holds zeros (the CG
+        entry then takes r = rhs without a pass over A)."""
         L = _bind()
         iters = ctypes.c_int64(0)
         resid = ctypes.c_double(0.0)
         w = [_ptr(t) for t in self._work]
         if self.solver_kind == "cg":
-            rc = L.amg_driver_cg(self.handle, _ptr(rhs), _ptr(x), *w, self.tol,
-                                 self.abstol, self.maxiter,
-                                 ctypes.byref(iters), ctypes.byref(resid))
+            rc = L.amg_driver_cg_fused(self.handle, _ptr(rhs), _ptr(x), *w,
+                                       int(bool(x_is_zero)), self.tol, self.abstol,
+                                       self.maxiter, ctypes.byref(iters),
+                                       ctypes.byref(resid))
         else:
             rc = L.amg_driver_bicgstab(self.handle, _ptr(rhs), _ptr(x), *w, self.tol,
                                        self.abstol, self.maxiter,

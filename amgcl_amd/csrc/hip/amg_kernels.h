@@ -49,6 +49,31 @@ int amg_sell_relax_f32(int64_t nrows, int64_t nslice, const int64_t *soff, const
 int amg_sell_fill_f64(int64_t nrows, int64_t nslice, const int *ptr, const int *col,
                       const double *val, const int64_t *soff, const int *srows, int *scol,
                       double *sval, hipStream_t stream);
+// fused passes on either image: off = soff (padded: srows optional, smask and
+// ptr null) or moff (compact: smask and the CSR ptr set)
+int amg_relax_zero_f64(int64_t n, const double *M, const double *rhs, double *xn,
+                       hipStream_t stream);
+int amg_relax_zero_f32(int64_t n, const float *M, const float *rhs, float *xn,
+                       hipStream_t stream);
+int amg_sell_zero_residual_f64(int64_t nrows, int64_t nslice, const int64_t *off,
+                               const int *col, const double *val, const int *srows,
+                               const uint64_t *smask, const int *ptr, const double *M,
+                               const double *rhs, double *u, double *t,
+                               hipStream_t stream);
+int amg_sell_zero_residual_f32(int64_t nrows, int64_t nslice, const int64_t *off,
+                               const int *col, const float *val, const int *srows,
+                               const uint64_t *smask, const int *ptr, const float *M,
+                               const float *rhs, float *u, float *t, hipStream_t stream);
+int amg_sell_relax_dot_f64(int64_t nrows, int64_t nslice, const int64_t *off,
+                           const int *col, const double *val, const int *srows,
+                           const uint64_t *smask, const int *ptr, const double *M,
+                           const double *rhs, const double *x, double *xn, double *out,
+                           hipStream_t stream);
+int amg_sell_pupdate_spmv_dot_f64(int64_t nrows, int64_t nslice, const int64_t *off,
+                                  const int *col, const double *val, const int *srows,
+                                  const uint64_t *smask, const int *ptr, const double *s,
+                                  const double *p, double beta, int first, double *p_new,
+                                  double *q, double *out, hipStream_t stream);
 // compact SELL-64 image (moff, smask, the CSR ptr, then the nnz-long scol/sval)
 int amg_sellc_spmv_f64(int64_t nrows, int64_t nslice, const int64_t *moff,
                        const uint64_t *smask, const int *ptr, const int *col,
@@ -160,6 +185,12 @@ int amg_driver_precond(void *h, const double *rhs, double *x, double *x_swap);
 int amg_driver_cg(void *h, const double *rhs, double *x, double *r, double *s, double *p,
                   double *q, double *s_swap, double tol, double abstol, int maxiter,
                   int64_t *iters_out, double *resid_out);
+// amg_driver_cg plus p_swap, the partner buffer of the fused p update (null:
+// the unfused sequence), and x_is_zero, the caller's word that x holds zeros
+int amg_driver_cg_fused(void *h, const double *rhs, double *x, double *r, double *s,
+                        double *p, double *q, double *s_swap, double *p_swap,
+                        int x_is_zero, double tol, double abstol, int maxiter,
+                        int64_t *iters_out, double *resid_out);
 int amg_driver_bicgstab(void *h, const double *rhs, double *x, double *r, double *p,
                         double *v, double *s2, double *t2, double *rh, double *T,
                         double *T_swap, double tol, double abstol, int maxiter,

@@ -559,7 +559,7 @@ extern "C" void *amgcl_amd_gpu_solver_create(int n, const int *ptr, const int *c
         delete S;
         return nullptr;
     }
-    int nwork = S->type == "cg" ? 5 : 8;
+    int nwork = S->type == "cg" ? 6 : 8;  // cg: r, s, p, q, s_swap, p_swap
     for (int i = 0; i < nwork; ++i) S->work.push_back(S->keep(dalloc(n)));
     S->rhs_d = S->keep(dalloc(n));
     S->x_d = S->keep(dalloc(n));
@@ -580,8 +580,9 @@ extern "C" int amgcl_amd_gpu_solver_solve(void *h, const double *rhs, double *x,
     int rc;
     auto &w = S->work;
     if (S->type == "cg")
-        rc = amg_driver_cg(S->driver, S->rhs_d, S->x_d, w[0], w[1], w[2], w[3], w[4],
-                           S->tol, 0.0, S->maxiter, &it, &res);
+        // x is the caller's initial guess, so it is not declared zero
+        rc = amg_driver_cg_fused(S->driver, S->rhs_d, S->x_d, w[0], w[1], w[2], w[3], w[4],
+                                 w[5], 0, S->tol, 0.0, S->maxiter, &it, &res);
     else
         rc = amg_driver_bicgstab(S->driver, S->rhs_d, S->x_d, w[0], w[1], w[2], w[3],
                                  w[4], w[5], w[6], w[7], S->tol, 0.0, S->maxiter,

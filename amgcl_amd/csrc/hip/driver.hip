@@ -52,6 +52,8 @@ AMG_BY_TYPE(sellc_relax)
 AMG_BY_TYPE(axpby)
 AMG_BY_TYPE(vmul)
 AMG_BY_TYPE(fill)
+AMG_BY_TYPE(relax_zero)
+AMG_BY_TYPE(sell_zero_residual)
 #undef AMG_BY_TYPE
 
 // x_new = x + M ∘ (rhs - A x), written to a separate buffer (pointer swap)
@@ -75,19 +77,11 @@ __global__ void relax_swap_k(int64_t nrows, const int *__restrict__ ptr,
     }
 }
 
-// first pre-smooth of a cycle starts from u = 0: x_new = M ∘ rhs (no A pass)
-template <typename T>
-__global__ void relax_zero_k(int64_t n, const T *__restrict__ M,
-                             const T *__restrict__ rhs, T *__restrict__ xn) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) xn[i] = M[i] * rhs[i];
-}
-
 struct GraphEntry {
     const double *rhs;
     double *x;
     double *xswap;
+    bool dot;  // the capture ends in the dot-carrying post-smooth (CG only)
     hipGraphExec_t exec;
 };
 
@@ -105,6 +99,10 @@ struct Driver {
     // tail being pure launch overhead) into a single graph launch.
     std::vector<GraphEntry> graphs;
     bool use_graphs;
+    // Vector kernels folded into SELL passes (sell_k modes 3 to 5) and the
+    // zero-guess entry of the Krylov loops; AMGCL_NO_FUSE=1 at create keeps
+    // the separate kernels, in the same build
+    bool fuse;
     // The solve runs on an internal non-blocking stream, event-chained to the
     // caller's (torch) stream at entry/exit.  The torch default stream is the
     // HIP *legacy* stream, which hipStreamBeginCapture cannot capture
@@ -294,16 +292,40 @@ static int relax_swap(Driver *D, const LevelDesc &L, const T *rhs, T **x, T **xn
     return (int)hipGetLastError();
 }
 
+// the smoother is the diagonal one and A carries a SELL image: the levels the
+// fused sell_k modes serve
+static bool diag_sell(const LevelDesc &L) {
+    return !L.spai1.nrows && !L.ilu_iters && !L.cheb_degree && !L.bsize && L.A.nslice;
+}
+
+// Whether the zero-guess smooth is folded into the residual pass (sell_k mode
+// 3).  The fold saves three vector passes per row and pays a second gather per
+// nonzero.  MEASURED (512^3, one MI355X, profiles/README.md): at 7 nnz/row the
+// fused pass takes 3.24 ms against 2.99 + 0.69 ms; on the coarse levels (32
+// to 68 nnz/row) it takes 1.98 ms against 1.07 + 0.03 ms.  By the first
+// figure seven gathers cost 0.25 of the 0.69 ms saved, which puts the
+// break-even near 19 nnz/row; 10 keeps a margin.
+static bool zero_residual_pays(const OpDesc &A) { return A.nnz <= 10 * A.nrows; }
+
+// the leading arguments of the fused SELL entry points, for either image
+#define SELL_IMAGE(A)                                                               \
+    (A).nrows, (A).nslice, (A).smask ? (A).moff : (A).soff, (A).scol,               \
+        (const T *)(A).sval, (A).smask ? nullptr : (A).srows, (A).smask,            \
+        (A).smask ? (A).ptr : nullptr
+
 // one multigrid cycle; *u_io holds the iterate buffer (may be swapped),
-// uses L.t as the swap partner / residual scratch
+// uses L.t as the swap partner / residual scratch.  dot_out (fp64, level 0 of
+// a diag_sell hierarchy with npost >= 1 only): the last post-smooth also
+// leaves f · u there.
 template <typename T>
-static int cycle(Driver *D, int li, const T *f, T **u_io, T **scratch, bool u_is_zero) {
+static int cycle(Driver *D, int li, const T *f, T **u_io, T **scratch, bool u_is_zero,
+                 double *dot_out = nullptr) {
     LevelDesc &L = D->lv[li];
     const bool coarsest = (li + 1 == (int)D->lv.size());
 
-    // relax_zero writes into the swap buffer and swaps, so zero-guess and
+    // zero_guess_relax writes into the swap buffer and swaps, so zero-guess and
     // general smooths have identical pointer parity (no copy-back needed)
-    auto relax_zero = [&](LevelDesc &LL, const T *ff, T **u2, T **sc) -> int {
+    auto zero_guess_relax = [&](LevelDesc &LL, const T *ff, T **u2, T **sc) -> int {
         // in place like its general form, so neither swaps
         if (LL.spai1.nrows > 0) return spai1_apply<T>(D, LL, ff, *u2, (T *)nullptr);
         if (LL.cheb_degree || LL.bsize || LL.ilu_iters) {
@@ -311,8 +333,7 @@ static int cycle(Driver *D, int li, const T *f, T **u_io, T **scratch, bool u_is
             CHK(fill<T>(LL.A.nrows, 0.0, *u2, D->stream));
             return relax_swap<T>(D, LL, ff, u2, sc);
         }
-        relax_zero_k<T><<<amg_nblocks(LL.A.nrows), 256, 0, D->stream>>>(
-            LL.A.nrows, (const T *)LL.M, ff, *sc);
+        CHK(relax_zero<T>(LL.A.nrows, (const T *)LL.M, ff, *sc, D->stream));
         std::swap(*u2, *sc);
         return 0;
     };
@@ -323,7 +344,7 @@ static int cycle(Driver *D, int li, const T *f, T **u_io, T **scratch, bool u_is
         } else {
             for (int i = 0; i < D->npre + D->npost; ++i) {
                 if (u_is_zero && i == 0) {
-                    CHK(relax_zero(L, f, u_io, scratch));
+                    CHK(zero_guess_relax(L, f, u_io, scratch));
                     continue;
                 }
                 CHK(relax_swap<T>(D, L, f, u_io, scratch));
@@ -333,15 +354,28 @@ static int cycle(Driver *D, int li, const T *f, T **u_io, T **scratch, bool u_is
     }
 
     LevelDesc &N = D->lv[li + 1];
+    bool have_residual = false;
     for (int i = 0; i < D->npre; ++i) {
         if (u_is_zero && i == 0) {
-            CHK(relax_zero(L, f, u_io, scratch));
+            if (D->fuse && D->npre == 1 && diag_sell(L) && zero_residual_pays(L.A)) {
+                // u = M ∘ f and t = f - A u in one pass over A.  Pointer
+                // parity as zero_guess_relax then level_residual: u lands in
+                // *scratch, swap, t in the new *scratch (the old u buffer,
+                // which this pass never reads)
+                const T *M = (const T *)L.M;
+                CHK(sell_zero_residual<T>(SELL_IMAGE(L.A), M, f, *scratch, *u_io,
+                                          D->stream));
+                std::swap(*u_io, *scratch);
+                have_residual = true;
+                continue;
+            }
+            CHK(zero_guess_relax(L, f, u_io, scratch));
             continue;
         }
         CHK(relax_swap<T>(D, L, f, u_io, scratch));
     }
     // t = f - A u ; f_next = R t
-    CHK(level_residual<T>(D, L, f, *u_io, *scratch));
+    if (!have_residual) CHK(level_residual<T>(D, L, f, *u_io, *scratch));
     CHK(op_spmv<T>(D, L.R, *scratch, 1.0, 0.0, (T *)N.f));
     T *nu = (T *)N.u;
     T *nscratch = (T *)N.t;
@@ -351,14 +385,25 @@ static int cycle(Driver *D, int li, const T *f, T **u_io, T **scratch, bool u_is
     }
     // u += P u_next
     CHK(op_spmv<T>(D, L.P, nu, 1.0, 1.0, *u_io));
-    for (int i = 0; i < D->npost; ++i)
+    for (int i = 0; i < D->npost; ++i) {
+        if constexpr (std::is_same_v<T, double>) {
+            if (dot_out && i == D->npost - 1) {
+                CHK(amg_sell_relax_dot_f64(SELL_IMAGE(L.A), L.M, f, *u_io, *scratch,
+                                           dot_out, D->stream));
+                std::swap(*u_io, *scratch);
+                continue;
+            }
+        }
         CHK(relax_swap<T>(D, L, f, u_io, scratch));
+    }
     return (int)hipGetLastError();
 }
 
 // fp64 in/out preconditioner application; in f32 mode the V-cycle runs on the
 // fp32 hierarchy between two cast kernels (backend/detail/mixing.hpp shape)
-static int precond_apply(Driver *D, const double *rhs, double *x, double *x_swap) {
+// with dot (cg_solve's dot_in_cycle), dotbuf_d[0] = rhs · x afterwards
+static int precond_apply(Driver *D, const double *rhs, double *x, double *x_swap,
+                         bool dot) {
     const int64_t n = D->lv[0].A.nrows;
     if (D->f32) {
         CHK(amg_cast_d2s(n, rhs, D->cb_r, D->stream));
@@ -372,7 +417,8 @@ static int precond_apply(Driver *D, const double *rhs, double *x, double *x_swap
     double *u = x;
     double *scratch = x_swap;
     for (int c = 0; c < D->pre_cycles; ++c)
-        CHK(cycle<double>(D, 0, rhs, &u, &scratch, c == 0));
+        CHK(cycle<double>(D, 0, rhs, &u, &scratch, c == 0,
+                          dot && c == D->pre_cycles - 1 ? D->dotbuf_d : nullptr));
     if (u != x)
         CHK(hipMemcpyAsync(x, u, n * sizeof(double), hipMemcpyDeviceToDevice, D->stream));
     return 0;
@@ -383,16 +429,16 @@ static int precond_apply(Driver *D, const double *rhs, double *x, double *x_swap
 // valid for every later call with the same buffer triple.  Falls back to the
 // direct path if capture fails (e.g. nested capture) or AMGCL_NO_GRAPH=1.
 static int precond_apply_graphed(Driver *D, const double *rhs, double *x,
-                                 double *x_swap) {
-    if (!D->use_graphs) return precond_apply(D, rhs, x, x_swap);
+                                 double *x_swap, bool dot = false) {
+    if (!D->use_graphs) return precond_apply(D, rhs, x, x_swap, dot);
     for (const GraphEntry &g : D->graphs)
-        if (g.rhs == rhs && g.x == x && g.xswap == x_swap)
+        if (g.rhs == rhs && g.x == x && g.xswap == x_swap && g.dot == dot)
             return (int)hipGraphLaunch(g.exec, D->stream);
-    if (D->graphs.size() >= 8) return precond_apply(D, rhs, x, x_swap);
+    if (D->graphs.size() >= 8) return precond_apply(D, rhs, x, x_swap, dot);
     if (hipStreamBeginCapture(D->stream, hipStreamCaptureModeThreadLocal) !=
         hipSuccess)
-        return precond_apply(D, rhs, x, x_swap);
-    int rc = precond_apply(D, rhs, x, x_swap);
+        return precond_apply(D, rhs, x, x_swap, dot);
+    int rc = precond_apply(D, rhs, x, x_swap, dot);
     hipGraph_t graph;
     hipError_t ec = hipStreamEndCapture(D->stream, &graph);
     if (rc) return rc;
@@ -404,9 +450,9 @@ static int precond_apply_graphed(Driver *D, const double *rhs, double *x,
         // capture succeeded but instantiation failed: run directly
         (void)hipGetLastError();
         D->use_graphs = false;
-        return precond_apply(D, rhs, x, x_swap);
+        return precond_apply(D, rhs, x, x_swap, dot);
     }
-    D->graphs.push_back({rhs, x, x_swap, exec});
+    D->graphs.push_back({rhs, x, x_swap, dot, exec});
     return (int)hipGraphLaunch(exec, D->stream);
 }
 
@@ -459,6 +505,8 @@ extern "C" void *amg_driver_create(const LevelDesc *levels, int nlevels,
     D->cb_r = D->cb_x = D->cb_s = nullptr;
     const char *ng = getenv("AMGCL_NO_GRAPH");
     D->use_graphs = !(ng && ng[0] && ng[0] != '0');
+    const char *nf = getenv("AMGCL_NO_FUSE");
+    D->fuse = !(nf && nf[0] && nf[0] != '0');
     D->ext_stream = stream;
     D->ev_in = D->ev_out = nullptr;
     hipStream_t st_int = nullptr;
@@ -572,9 +620,11 @@ struct Krylov {
 // Shared entry of the Krylov loops: ||rhs||, eps, r = rhs - A x (copied to
 // r_copy if given: BiCGStab's shadow residual) and ||r||.  A zero rhs is
 // solved by x = 0: res = eps = 0 then keeps the caller's loop from starting.
+// With x_is_zero (the caller's word that x holds zeros) r = rhs and
+// ||r|| = ||rhs|| exactly, so the A pass and the second dot are left out.
 static int krylov_begin(Driver *D, const FineOp &A, const double *rhs, double *x,
                         double *r, double *r_copy, double tol, double abstol,
-                        Krylov *k) {
+                        bool x_is_zero, Krylov *k) {
     const int64_t n = A.op.nrows;
     hipStream_t st = D->stream;
     double dot;
@@ -584,9 +634,16 @@ static int krylov_begin(Driver *D, const FineOp &A, const double *rhs, double *x
     k->eps = k->res = 0.0;
     if (k->norm_rhs == 0.0) return amg_fill_f64(n, 0.0, x, st);
     k->eps = tol * k->norm_rhs > abstol ? tol * k->norm_rhs : abstol;
-    CHK(A.residual(rhs, x, r));
+    if (x_is_zero && D->fuse)
+        CHK(hipMemcpyAsync(r, rhs, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    else
+        CHK(A.residual(rhs, x, r));
     if (r_copy)
         CHK(hipMemcpyAsync(r_copy, r, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (x_is_zero && D->fuse) {
+        k->res = k->norm_rhs;
+        return 0;
+    }
     CHK(amg_dot_f64(n, r, r, D->dotbuf_d, st));
     CHK(read_dots(D, 1, &dot));
     k->res = sqrt(dot);
@@ -603,31 +660,49 @@ static int krylov_end(const Krylov &k, int64_t iter, int64_t *iters_out,
 
 // Preconditioned CG (parity: amgcl/solver/cg.hpp:152-204).
 // Work vectors r,s,p,q + s_swap provided by the caller (device, n doubles).
+// Two fusions, each with today's sequence as its other branch:
+//   rho = r·s rides on the cycle's last post-smooth, which reads r and writes
+//   s row by row (fp64 cycle, npost >= 1, diag_sell fine level);
+//   p = s + beta p, q = A p and p·q are one SELL pass when the caller gives
+//   p_swap and the fine operator has a SELL image; p and p_swap then swap.
 static int cg_solve(Driver *D, const double *rhs, double *x, double *r, double *s,
-                    double *p, double *q, double *s_swap, double tol, double abstol,
-                    int maxiter, int64_t *iters_out, double *resid_out) {
+                    double *p, double *q, double *s_swap, double *p_swap, bool x_is_zero,
+                    double tol, double abstol, int maxiter, int64_t *iters_out,
+                    double *resid_out) {
     const FineOp A(D);
     const int64_t n = A.op.nrows;
     hipStream_t st = D->stream;
     double dots[2];
     Krylov k;
-    CHK(krylov_begin(D, A, rhs, x, r, nullptr, tol, abstol, &k));
+    CHK(krylov_begin(D, A, rhs, x, r, nullptr, tol, abstol, x_is_zero, &k));
+    const bool dot_in_cycle = D->fuse && !D->f32 && D->npost >= 1 && D->pre_cycles >= 1 &&
+                              D->lv.size() > 1 && diag_sell(D->lv[0]);
+    const bool fuse_p = D->fuse && p_swap && !A.bsr && A.op.nslice;
 
     double rho1 = 0.0, rho2 = 0.0;
     int64_t iter = 0;
     while (k.res > k.eps && iter < maxiter) {
-        CHK(precond_apply_graphed(D, r, s, s_swap));
+        CHK(precond_apply_graphed(D, r, s, s_swap, dot_in_cycle));
         rho2 = rho1;
-        CHK(amg_dot_f64(n, r, s, D->dotbuf_d, st));
+        if (!dot_in_cycle) CHK(amg_dot_f64(n, r, s, D->dotbuf_d, st));
         CHK(read_dots(D, 1, dots));
         rho1 = dots[0];
-        if (iter == 0) {
-            CHK(hipMemcpyAsync(p, s, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+        if (fuse_p) {
+            using T = double;  // SELL_IMAGE casts sval
+            CHK(amg_sell_pupdate_spmv_dot_f64(SELL_IMAGE(A.op), s, p,
+                                              iter == 0 ? 0.0 : rho1 / rho2, iter == 0,
+                                              p_swap, q, D->dotbuf_d, st));
+            std::swap(p, p_swap);
         } else {
-            CHK(amg_axpby_f64(n, 1.0, s, rho1 / rho2, p, st));
+            if (iter == 0) {
+                CHK(hipMemcpyAsync(p, s, n * sizeof(double), hipMemcpyDeviceToDevice,
+                                   st));
+            } else {
+                CHK(amg_axpby_f64(n, 1.0, s, rho1 / rho2, p, st));
+            }
+            CHK(A.spmv(p, 1.0, 0.0, q));
+            CHK(amg_dot_f64(n, q, p, D->dotbuf_d, st));
         }
-        CHK(A.spmv(p, 1.0, 0.0, q));
-        CHK(amg_dot_f64(n, q, p, D->dotbuf_d, st));
         CHK(read_dots(D, 1, dots));
         double alpha = rho1 / dots[0];
         // fused x/r update + residual norm (single pass over x,r,p,q)
@@ -639,14 +714,25 @@ static int cg_solve(Driver *D, const double *rhs, double *x, double *r, double *
     return krylov_end(k, iter, iters_out, resid_out);
 }
 
+#undef SELL_IMAGE
+
 extern "C" int amg_driver_cg(void *h, const double *rhs, double *x, double *r, double *s,
                              double *p, double *q, double *s_swap, double tol,
                              double abstol, int maxiter, int64_t *iters_out,
                              double *resid_out) {
+    return amg_driver_cg_fused(h, rhs, x, r, s, p, q, s_swap, nullptr, 0, tol, abstol,
+                               maxiter, iters_out, resid_out);
+}
+
+extern "C" int amg_driver_cg_fused(void *h, const double *rhs, double *x, double *r,
+                                   double *s, double *p, double *q, double *s_swap,
+                                   double *p_swap, int x_is_zero, double tol,
+                                   double abstol, int maxiter, int64_t *iters_out,
+                                   double *resid_out) {
     Driver *D = (Driver *)h;
     CHK(enter_driver(D));
-    return finish(D, cg_solve(D, rhs, x, r, s, p, q, s_swap, tol, abstol, maxiter,
-                              iters_out, resid_out), /*sync=*/true);
+    return finish(D, cg_solve(D, rhs, x, r, s, p, q, s_swap, p_swap, x_is_zero != 0, tol,
+                              abstol, maxiter, iters_out, resid_out), /*sync=*/true);
 }
 
 // Preconditioned BiCGStab, right-preconditioned
@@ -661,7 +747,7 @@ static int bicgstab_solve(Driver *D, const double *rhs, double *x, double *r, do
     hipStream_t st = D->stream;
     double dots[2];
     Krylov k;
-    CHK(krylov_begin(D, A, rhs, x, r, rh, tol, abstol, &k));
+    CHK(krylov_begin(D, A, rhs, x, r, rh, tol, abstol, /*x_is_zero=*/false, &k));
 
     double rho1 = 0.0, rho2 = 0.0, alpha = 0.0, omega = 0.0;
     int64_t iter = 0;

@@ -210,7 +210,38 @@ extern "C" int amg_relax_diag_f32(int64_t nrows, int64_t nnz, const int *ptr,
 // terms of the padding are gone.  The slice index is made wave-uniform, so
 // masks and the running entry offset stay in scalar registers; the masks of
 // SELLC_U slots are fetched ahead of the loads that depend on them.
+//
+// Modes 3 to 5 fold a neighbouring vector kernel into the pass.  The value a
+// lane gathers for column c (sell_operand) is then computed from the vectors
+// the folded kernel would have read, by the expression that kernel uses, so it
+// is the double (or float) the unfused sequence stores and reads back:
+//   3  zero-guess smooth + residual: operand M[c] rhs[c] (relax_zero_k);
+//      y2 = M rhs, y = rhs - A y2
+//   4  mode 2, plus out[0] += sum rhs[row] xn[row]
+//   5  p update + spmv + dot: operand p_new[c] = x[c] + beta x2[c] (axpby_k with
+//      a = 1), or x[c] alone when `first` (x2 is then never read);
+//      y2 = p_new, y = A p_new, out[0] += sum y[row] p_new[row]
+// The sums of modes 4 and 5 are reduced as in dot_k: per lane over the
+// grid-stride loop, wave shuffle, one atomicAdd per block; the launcher
+// zeroes out first.
 #define SELLC_U 4
+template <typename T, int MODE>
+__device__ __forceinline__ T sell_operand(int64_t c, const T *__restrict__ x,
+                                          const T *__restrict__ x2, double beta,
+                                          int first, const T *__restrict__ rhs,
+                                          const T *__restrict__ M) {
+    // the operand is a value of its own: fast-math must not regroup its
+    // product with the val * operand product around it
+#pragma clang fp reassociate(off)
+    if (MODE == 3) return M[c] * rhs[c];
+    if (MODE == 5) {
+        if (first) return x[c];
+        // a x + b y as axpby_k rounds it for a = 1: one fma onto the exact 1 x
+        return (T)__builtin_fma(beta, (double)x2[c], (double)x[c]);
+    }
+    return x[c];
+}
+
 template <typename T, int MODE, bool COMPACT>  // 0: y=aAx+by  1: r=rhs-Ax  2: xn=x+M(rhs-Ax)
 __global__ void sell_k(int64_t nrows, int64_t nslice,
                        const int64_t *__restrict__ soff,  // COMPACT: moff
@@ -219,12 +250,15 @@ __global__ void sell_k(int64_t nrows, int64_t nslice,
                        const uint64_t *__restrict__ smask, const int *__restrict__ ptr,
                        const T *__restrict__ x,
                        double alpha, double beta, const T *__restrict__ rhs,
-                       const T *__restrict__ M, T *__restrict__ y) {
+                       const T *__restrict__ M, T *__restrict__ y,
+                       const T *__restrict__ x2, T *__restrict__ y2,
+                       double *__restrict__ out, int first) {
     const int wpb = blockDim.x / WAVE;
     int wid = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
     if (COMPACT) wid = __builtin_amdgcn_readfirstlane(wid);
     int64_t s = (int64_t)blockIdx.x * wpb + wid;
     int64_t sstride = (int64_t)gridDim.x * wpb;
+    double dsum = 0.0;  // modes 4, 5: this lane's share of the dot
     for (; s < nslice; s += sstride) {
         double acc = 0.0;
         if (COMPACT) {
@@ -257,7 +291,8 @@ __global__ void sell_k(int64_t nrows, int64_t nslice,
 #pragma unroll
                 for (int k = 0; k < SELLC_U; ++k) {
                     xv[k] = (T)0;
-                    if ((m[k] >> lane) & 1) xv[k] = x[c[k]];
+                    if ((m[k] >> lane) & 1)
+                        xv[k] = sell_operand<T, MODE>(c[k], x, x2, beta, first, rhs, M);
                 }
 #pragma unroll
                 for (int k = 0; k < SELLC_U; ++k) acc += (double)v[k] * (double)xv[k];
@@ -265,7 +300,8 @@ __global__ void sell_k(int64_t nrows, int64_t nslice,
         } else {
             int64_t beg = soff[s], end = soff[s + 1];
             for (int64_t j = beg + lane; j < end; j += WAVE)
-                acc += (double)val[j] * (double)x[col[j]];
+                acc += (double)val[j] *
+                       (double)sell_operand<T, MODE>(col[j], x, x2, beta, first, rhs, M);
         }
         int64_t row = (!COMPACT && srows) ? (int64_t)srows[s * WAVE + lane] : s * WAVE + lane;
         if (row >= 0 && row < nrows) {
@@ -274,10 +310,29 @@ __global__ void sell_k(int64_t nrows, int64_t nslice,
                                          : alpha * acc + beta * (double)y[row]);
             else if (MODE == 1)
                 y[row] = (T)((double)rhs[row] - acc);
-            else
-                y[row] = (T)((double)x[row] +
-                             (double)M[row] * ((double)rhs[row] - acc));
+            else if (MODE == 2 || MODE == 4) {
+                T xn = (T)((double)x[row] +
+                           (double)M[row] * ((double)rhs[row] - acc));
+                y[row] = xn;
+                if (MODE == 4) dsum += (double)rhs[row] * (double)xn;
+            } else if (MODE == 3) {
+                y2[row] = sell_operand<T, MODE>(row, x, x2, beta, first, rhs, M);
+                y[row] = (T)((double)rhs[row] - acc);
+            } else {
+                T pn = sell_operand<T, MODE>(row, x, x2, beta, first, rhs, M);
+                y2[row] = pn;
+                y[row] = (T)acc;
+                dsum += acc * (double)pn;
+            }
         }
+    }
+    if (MODE == 4 || MODE == 5) {
+        __shared__ double lds[4];  // 256 threads = 4 waves
+#pragma unroll
+        for (int off = WAVE / 2; off > 0; off >>= 1) dsum += __shfl_down(dsum, off, WAVE);
+        if (lane == 0) lds[wid] = dsum;
+        __syncthreads();
+        if (threadIdx.x == 0) atomicAdd(out, lds[0] + lds[1] + lds[2] + lds[3]);
     }
 }
 
@@ -286,7 +341,8 @@ static int launch_sell(int64_t nrows, int64_t nslice, const int64_t *soff, const
                        const T *val, const int *srows, const T *x, double alpha,
                        double beta, const T *rhs, const T *M, T *y, hipStream_t stream) {
     sell_k<T, MODE, false><<<amg_nblocks(nslice * WAVE), 256, 0, stream>>>(
-        nrows, nslice, soff, col, val, srows, nullptr, nullptr, x, alpha, beta, rhs, M, y);
+        nrows, nslice, soff, col, val, srows, nullptr, nullptr, x, alpha, beta, rhs, M, y,
+        nullptr, nullptr, nullptr, 0);
     return (int)hipGetLastError();
 }
 
@@ -296,7 +352,33 @@ static int launch_sellc(int64_t nrows, int64_t nslice, const int64_t *moff,
                         const T *val, const T *x, double alpha, double beta, const T *rhs,
                         const T *M, T *y, hipStream_t stream) {
     sell_k<T, MODE, true><<<amg_nblocks(nslice * WAVE), 256, 0, stream>>>(
-        nrows, nslice, moff, col, val, nullptr, smask, ptr, x, alpha, beta, rhs, M, y);
+        nrows, nslice, moff, col, val, nullptr, smask, ptr, x, alpha, beta, rhs, M, y,
+        nullptr, nullptr, nullptr, 0);
+    return (int)hipGetLastError();
+}
+
+template <typename T>
+__global__ void fill_k(int64_t n, double v, T *__restrict__ x);  // vector primitives, below
+
+// The fused modes 3 to 5 on either image: an operator with smask set is
+// compact (soff_or_moff = moff), else padded.  x2/y2/out/first as in sell_k;
+// out (modes 4, 5) is zeroed on the stream first, as launch_dot does.
+template <typename T, int MODE>
+static int launch_sell_fused(int64_t nrows, int64_t nslice, const int64_t *soff_or_moff,
+                             const int *col, const T *val, const int *srows,
+                             const uint64_t *smask, const int *ptr, const T *x,
+                             const T *x2, double beta, const T *rhs, const T *M, T *y,
+                             T *y2, double *out, int first, hipStream_t stream) {
+    if (out) fill_k<double><<<1, 64, 0, stream>>>(1, 0.0, out);
+    const int grid = amg_nblocks(nslice * WAVE);
+    if (smask)
+        sell_k<T, MODE, true><<<grid, 256, 0, stream>>>(
+            nrows, nslice, soff_or_moff, col, val, nullptr, smask, ptr, x, 0.0, beta, rhs,
+            M, y, x2, y2, out, first);
+    else
+        sell_k<T, MODE, false><<<grid, 256, 0, stream>>>(
+            nrows, nslice, soff_or_moff, col, val, srows, nullptr, nullptr, x, 0.0, beta,
+            rhs, M, y, x2, y2, out, first);
     return (int)hipGetLastError();
 }
 
@@ -343,6 +425,61 @@ extern "C" int amg_sell_relax_f32(int64_t nrows, int64_t nslice, const int64_t *
                                   float *xn, hipStream_t stream) {
     return launch_sell<float, 2>(nrows, nslice, soff, col, val, srows, x, 0.0, 0.0, rhs,
                                  M, xn, stream);
+}
+
+// first pre-smooth of a cycle starts from u = 0: x_new = M ∘ rhs (no A pass)
+template <typename T>
+__global__ void relax_zero_k(int64_t n, const T *__restrict__ M,
+                             const T *__restrict__ rhs, T *__restrict__ xn) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) xn[i] = M[i] * rhs[i];
+}
+
+// Fused passes (sell_k modes 3 to 5).  One entry per mode serves both images:
+// off is soff (padded; srows optional, smask and ptr null) or moff (compact;
+// smask and the CSR ptr set, srows null).
+#define AMG_ZERO_GUESS_ENTRIES(T, SFX)                                                     \
+    extern "C" int amg_relax_zero_##SFX(int64_t n, const T *M, const T *rhs, T *xn,        \
+                                        hipStream_t stream) {                              \
+        relax_zero_k<T><<<amg_nblocks(n), 256, 0, stream>>>(n, M, rhs, xn);                \
+        return (int)hipGetLastError();                                                     \
+    }                                                                                      \
+    /* u = M ∘ rhs, t = rhs - A u */                                                       \
+    extern "C" int amg_sell_zero_residual_##SFX(                                           \
+        int64_t nrows, int64_t nslice, const int64_t *off, const int *col, const T *val,   \
+        const int *srows, const uint64_t *smask, const int *ptr, const T *M, const T *rhs, \
+        T *u, T *t, hipStream_t stream) {                                                  \
+        return launch_sell_fused<T, 3>(nrows, nslice, off, col, val, srows, smask, ptr,    \
+                                       nullptr, nullptr, 0.0, rhs, M, t, u, nullptr, 0,    \
+                                       stream);                                            \
+    }
+AMG_ZERO_GUESS_ENTRIES(double, f64)
+AMG_ZERO_GUESS_ENTRIES(float, f32)
+#undef AMG_ZERO_GUESS_ENTRIES
+
+// xn = x + M ∘ (rhs - A x), out[0] = rhs · xn
+extern "C" int amg_sell_relax_dot_f64(int64_t nrows, int64_t nslice, const int64_t *off,
+                                      const int *col, const double *val, const int *srows,
+                                      const uint64_t *smask, const int *ptr,
+                                      const double *M, const double *rhs, const double *x,
+                                      double *xn, double *out, hipStream_t stream) {
+    return launch_sell_fused<double, 4>(nrows, nslice, off, col, val, srows, smask, ptr, x,
+                                        nullptr, 0.0, rhs, M, xn, nullptr, out, 0, stream);
+}
+
+// p_new = s + beta p (p_new = s when first; p is then not read), q = A p_new,
+// out[0] = q · p_new.  p_new must not alias p.
+extern "C" int amg_sell_pupdate_spmv_dot_f64(int64_t nrows, int64_t nslice,
+                                             const int64_t *off, const int *col,
+                                             const double *val, const int *srows,
+                                             const uint64_t *smask, const int *ptr,
+                                             const double *s, const double *p, double beta,
+                                             int first, double *p_new, double *q,
+                                             double *out, hipStream_t stream) {
+    return launch_sell_fused<double, 5>(nrows, nslice, off, col, val, srows, smask, ptr, s,
+                                        p, beta, nullptr, nullptr, q, p_new, out, first,
+                                        stream);
 }
 
 // CSR -> SELL-64 fill: one wave per slice, iterating the element index i so

@@ -61,7 +61,7 @@ class MakeSolver:
         else:
             x_dev = x if not isinstance(x, np.ndarray) or b.name == "cpu" else b.from_host(x)
         if self._native is not None and A is None:
-            iters, resid = self._native.solve(rhs_dev, x_dev)
+            iters, resid = self._native.solve(rhs_dev, x_dev, x_is_zero=x is None)
         else:
             iters, resid = self.S(self.P, rhs_dev, x_dev, A=A)
         return x_dev, iters, resid
